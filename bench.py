@@ -11,6 +11,15 @@ Run single GPU:  python bench.py --gpus 1 --steps 50 --warmup 10
 Multi GPU (driver): python -m torch.distributed.run --nnodes=1
     --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
+A plain run sets up, warms up, times ``--steps`` rounds and prints one JSON
+result line; nothing else is measured. ``--dump-outputs DIR`` additionally
+writes what the timed rounds computed (see :func:`dump_outputs`) so two
+builds can be compared output for output: the dataset, the initial models
+and the schedule are all seeded, so equal arguments give equal inputs.
+``--full`` is the switch for any extra measurement (baselines, other
+configurations); the flagship has none, so today it runs the same
+benchmark — the per-config benchmarks live in ``benchmarks/``.
+
 The reference (measured on CPU) does 0.79 rounds/sec at 1000
 nodes = 790 node-rounds/sec; ``vs_baseline`` is value / 790.
 """
@@ -30,6 +39,39 @@ D_IN, N_CLASSES = 57, 2
 DELTA = 100
 SAMPLES_PER_SHARD_SET = 4601  # spambase-shaped synthetic, per 1000 nodes
 BASELINE_NODE_ROUNDS_PER_SEC = 0.79 * 1000
+DUMP_BUDGET_BYTES = 64 * 2**20
+
+
+def dump_outputs(out_dir: str, params, ages, evals) -> None:
+    """Write what the last timed round left a caller with, as ``.npy``:
+
+    * ``params.npy``  — float32 ``[rows, D]`` node models (``gather_params``)
+    * ``ages.npy``    — float64 ``[rows]`` model ages (``gather_ages``)
+    * ``rows.npy``    — float64 node ids of the rows above (all nodes unless
+      the full matrix would not fit the 64 MB budget; then a fixed seeded
+      sample)
+    * ``eval_last.npy`` — float64 metrics of the last evaluation sweep, in
+      sorted metric-name order (absent if no sweep ran)
+    """
+    os.makedirs(out_dir, exist_ok=True)
+    params = params.detach().to("cpu", torch.float32).numpy()
+    ages = ages.detach().to("cpu", torch.float64).numpy().reshape(-1)
+    n = params.shape[0]
+    # params (4 B/elem) + ages and rows (8 B each) per node, metrics are tiny
+    per_row = 4 * params.shape[1] + 16
+    keep = (DUMP_BUDGET_BYTES - 4096) // per_row
+    rows = np.arange(n)
+    if n > keep:
+        rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+    np.save(os.path.join(out_dir, "params.npy"), params[rows])
+    np.save(os.path.join(out_dir, "ages.npy"), ages[rows])
+    np.save(os.path.join(out_dir, "rows.npy"), rows.astype(np.float64))
+    if evals:
+        last = evals[-1][1]
+        np.save(
+            os.path.join(out_dir, "eval_last.npy"),
+            np.array([last[k] for k in sorted(last)], dtype=np.float64),
+        )
 
 
 def main() -> None:
@@ -38,7 +80,17 @@ def main() -> None:
     ap.add_argument("--steps", type=int, default=30, help="rounds to time")
     ap.add_argument("--warmup", type=int, default=5, help="untimed rounds")
     ap.add_argument("--nodes-per-gpu", type=int, default=NODES_PER_GPU)
+    ap.add_argument(
+        "--dump-outputs", metavar="DIR", default=None,
+        help="after the timed rounds, write their outputs as DIR/<name>.npy",
+    )
+    ap.add_argument(
+        "--full", action="store_true",
+        help="also run every extra measurement (the flagship has none)",
+    )
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", 1))
     rank = int(os.environ.get("RANK", 0))
@@ -124,6 +176,14 @@ def main() -> None:
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+
+    if args.dump_outputs:
+        # the gathers are collective; rank 0 holds the result and writes it
+        params, ages = sim.gather_params(), sim.gather_ages()
+        if rank == 0:
+            dump_outputs(
+                args.dump_outputs, params, ages, report.get_evaluation(False)
+            )
 
     rounds_per_sec = args.steps / elapsed
     value = rounds_per_sec * n_nodes  # whole-job aggregate: node-rounds/sec

@@ -72,7 +72,8 @@ def _engine_run(rounds=10):
         model_size=116, sampling_eval=0.3, seed=42,
     )
     sim = BatchedGossipSimulator(
-        cfg, LogRegSpec(d_in=D, n_classes=2, lr=0.1), data
+        cfg, LogRegSpec(d_in=D, n_classes=2, lr=0.1), data,
+        device=torch.device("cpu"),  # the arena above lives on the host
     )
     rep = SimulationReport()
     sim.add_receiver(rep)

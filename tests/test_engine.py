@@ -28,6 +28,11 @@ from gossipy_amd.engine import (
 )
 from gossipy_amd.simul import SimulationReport
 
+# every test in this module runs the engine on the host: the arenas are built
+# on the CPU, so the simulators are pinned there too (their default device is
+# the GPU whenever one is present)
+CPU = torch.device("cpu")
+
 
 def _make_data(n_nodes, d=57, n_samples=500, seed=0, margin=2.0, pm1=False):
     X, y = make_synthetic_classification((n_samples, d, 2), seed=seed, margin=margin)
@@ -177,7 +182,7 @@ class TestEngineCPU:
         base.update(cfg_kw)
         cfg = EngineConfig(**base)
         spec = LogRegSpec(d_in=57, n_classes=2, lr=0.1)
-        sim = BatchedGossipSimulator(cfg, spec, data)
+        sim = BatchedGossipSimulator(cfg, spec, data, device=CPU)
         rep = SimulationReport()
         sim.add_receiver(rep)
         sim.init_nodes()
@@ -221,7 +226,9 @@ class TestEngineCPU:
             sampling_eval=0.3,
             seed=4,
         )
-        sim = BatchedGossipSimulator(cfg, PegasosSpec(d_in=57, lam=0.01), data)
+        sim = BatchedGossipSimulator(
+            cfg, PegasosSpec(d_in=57, lam=0.01), data, device=CPU
+        )
         rep = SimulationReport()
         sim.add_receiver(rep)
         sim.init_nodes()
@@ -479,7 +486,7 @@ class TestPartitioned:
             d_in=57, n_classes=2, lr=0.1, n_parts=4,
             mode=mode or CreateModelMode.MERGE_UPDATE,
         )
-        sim = BatchedGossipSimulator(cfg, spec, data)
+        sim = BatchedGossipSimulator(cfg, spec, data, device=CPU)
         rep = SimulationReport()
         sim.add_receiver(rep)
         sim.init_nodes()
@@ -595,6 +602,7 @@ class TestTokenizedEngine:
             data,
             token_account=account or RandomizedTokenAccount(C=20, A=10),
             utility_fun=utility,
+            device=CPU,
         )
         rep = SimulationReport()
         sim.add_receiver(rep)
@@ -656,7 +664,8 @@ class TestTokenizedEngine:
         )
         spec = LogRegSpec(d_in=57, n_classes=2, lr=0.1, n_parts=4)
         sim = BatchedTokenizedGossipSimulator(
-            cfg, spec, data, token_account=RandomizedTokenAccount(C=20, A=10)
+            cfg, spec, data, token_account=RandomizedTokenAccount(C=20, A=10),
+            device=CPU,
         )
         rep = SimulationReport()
         sim.add_receiver(rep)
@@ -687,7 +696,9 @@ class TestAll2AllEngine:
         base.update(cfg_kw)
         cfg = EngineConfig(**base)
         spec = LogRegSpec(d_in=57, n_classes=2, lr=0.1)
-        sim = BatchedAll2AllGossipSimulator(cfg, spec, data, mixing=mixing)
+        sim = BatchedAll2AllGossipSimulator(
+            cfg, spec, data, mixing=mixing, device=CPU
+        )
         rep = SimulationReport()
         sim.add_receiver(rep)
         sim.init_nodes()
@@ -738,7 +749,7 @@ class TestAll2AllEngine:
         from gossipy_amd.engine import BatchedAll2AllGossipSimulator
 
         spec = LogRegSpec(d_in=57, n_classes=2, lr=0.1)
-        ref = BatchedAll2AllGossipSimulator(cfg, spec, data)
+        ref = BatchedAll2AllGossipSimulator(cfg, spec, data, device=CPU)
         ref.init_nodes()
         ref.start(n_rounds=3)
 
@@ -799,7 +810,7 @@ class TestEngineCheckpoint:
             delay=UniformDelay(0, 12), **(cfg_kw or {}),
         )
         spec = LogRegSpec(d_in=57, n_classes=2, lr=0.1, **(spec_kw or {}))
-        sim = BatchedGossipSimulator(cfg, spec, data)
+        sim = BatchedGossipSimulator(cfg, spec, data, device=CPU)
         sim.init_nodes()
         return sim
 
@@ -846,6 +857,7 @@ class TestEngineCheckpoint:
             sim = BatchedTokenizedGossipSimulator(
                 cfg, LogRegSpec(d_in=57, n_classes=2, lr=0.1), data,
                 token_account=RandomizedTokenAccount(C=20, A=10),
+                device=CPU,
             )
             sim.init_nodes()
             return sim
@@ -887,6 +899,7 @@ class TestEngineCheckpoint:
         sim = BatchedTokenizedGossipSimulator(
             cfg, LogRegSpec(d_in=57, n_classes=2, lr=0.1), data,
             token_account=RandomizedTokenAccount(C=20, A=10),
+            device=CPU,
         )
         sim.init_nodes()
         sim.start(n_rounds=2)
@@ -911,7 +924,7 @@ class TestEngineCheckpoint:
         )
         sim = BatchedPENSGossipSimulator(
             cfg, LogRegSpec(d_in=57, n_classes=2, lr=0.1), data,
-            n_sampled=4, m_top=2, step1_rounds=step1_rounds,
+            n_sampled=4, m_top=2, step1_rounds=step1_rounds, device=CPU,
         )
         sim.init_nodes()
         return sim
@@ -931,7 +944,7 @@ class TestEngineCheckpoint:
                 n_nodes=8, delta=5, protocol=AntiEntropyProtocol.PUSH,
                 model_size=spec.D, sampling_eval=0.0, seed=41,
             )
-            sim = BatchedGossipSimulator(cfg, spec, data)
+            sim = BatchedGossipSimulator(cfg, spec, data, device=CPU)
             sim.init_nodes()
             return sim
 
@@ -1002,7 +1015,7 @@ class TestSampledEngine:
         base.update(cfg_kw)
         cfg = EngineConfig(**base)
         spec = LogRegSpec(d_in=57, n_classes=2, lr=0.1, sample_size=sample)
-        sim = BatchedGossipSimulator(cfg, spec, data)
+        sim = BatchedGossipSimulator(cfg, spec, data, device=CPU)
         rep = SimulationReport()
         sim.add_receiver(rep)
         sim.init_nodes()
@@ -1147,7 +1160,7 @@ class TestMFEngine:
         )
         base.update(cfg_kw)
         cfg = EngineConfig(**base)
-        sim = BatchedGossipSimulator(cfg, self._spec(), data)
+        sim = BatchedGossipSimulator(cfg, self._spec(), data, device=CPU)
         rep = SimulationReport()
         sim.add_receiver(rep)
         sim.init_nodes()
@@ -1250,7 +1263,7 @@ class TestKMeansEngine:
         spec = KMeansSpec(
             k=3, dim=8, alpha=0.1, mode=CreateModelMode.MERGE_UPDATE
         )
-        sim = BatchedGossipSimulator(cfg, spec, data)
+        sim = BatchedGossipSimulator(cfg, spec, data, device=CPU)
         rep = SimulationReport()
         sim.add_receiver(rep)
         sim.init_nodes()
@@ -1285,7 +1298,7 @@ class TestPassThroughEngine:
         base.update(cfg_kw)
         cfg = EngineConfig(**base)
         spec = LogRegSpec(d_in=57, n_classes=2, lr=0.1, pass_through=True)
-        sim = BatchedGossipSimulator(cfg, spec, data)
+        sim = BatchedGossipSimulator(cfg, spec, data, device=CPU)
         rep = SimulationReport()
         sim.add_receiver(rep)
         sim.init_nodes()
@@ -1356,7 +1369,7 @@ class TestCacheNeighEngine:
         base.update(cfg_kw)
         cfg = EngineConfig(**base)
         spec = LogRegSpec(d_in=57, n_classes=2, lr=0.1)
-        sim = BatchedCacheNeighGossipSimulator(cfg, spec, data)
+        sim = BatchedCacheNeighGossipSimulator(cfg, spec, data, device=CPU)
         rep = SimulationReport()
         sim.add_receiver(rep)
         sim.init_nodes()
@@ -1396,7 +1409,8 @@ class TestPENSEngine:
         cfg = EngineConfig(**base)
         spec = LogRegSpec(d_in=57, n_classes=2, lr=0.1)
         sim = BatchedPENSGossipSimulator(
-            cfg, spec, data, n_sampled=4, m_top=2, step1_rounds=step1_rounds
+            cfg, spec, data, n_sampled=4, m_top=2, step1_rounds=step1_rounds,
+            device=CPU,
         )
         rep = SimulationReport()
         sim.add_receiver(rep)
@@ -1433,7 +1447,7 @@ class TestPENSEngine:
             model_size=spec.D, sampling_eval=0.0, seed=37,
         )
         sim = BatchedPENSGossipSimulator(
-            cfg, spec, data, n_sampled=3, m_top=1, step1_rounds=4,
+            cfg, spec, data, n_sampled=3, m_top=1, step1_rounds=4, device=CPU,
         )
         rep = SimulationReport()
         sim.add_receiver(rep)
@@ -1779,7 +1793,7 @@ class TestTorchModuleEngine:
             n_nodes=8, delta=5, protocol=AntiEntropyProtocol.PUSH,
             model_size=spec.D, sampling_eval=0.0, seed=41,
         )
-        sim = BatchedGossipSimulator(cfg, spec, data)
+        sim = BatchedGossipSimulator(cfg, spec, data, device=CPU)
         rep = SimulationReport()
         sim.add_receiver(rep)
         sim.init_nodes()
@@ -1796,7 +1810,7 @@ class TestTorchModuleEngine:
                 n_nodes=8, delta=5, protocol=AntiEntropyProtocol.PUSH,
                 model_size=spec.D, sampling_eval=0.0, seed=41,
             )
-            sim = BatchedGossipSimulator(cfg, spec, data)
+            sim = BatchedGossipSimulator(cfg, spec, data, device=CPU)
             sim.init_nodes()
             sim.start(n_rounds=2)
             return sim
@@ -1883,7 +1897,7 @@ class TestTorchModuleEngine:
                 n_nodes=8, delta=5, protocol=protocol,
                 model_size=spec.D, sampling_eval=0.0, seed=41,
             )
-            sim = BatchedGossipSimulator(cfg, spec, data)
+            sim = BatchedGossipSimulator(cfg, spec, data, device=CPU)
             sim.init_nodes()
             sim.start(n_rounds=rounds)
             return sim
@@ -2033,7 +2047,9 @@ def test_round_timer_records_rounds():
         n_nodes=20, delta=5, protocol=AntiEntropyProtocol.PUSH,
         model_size=116, sampling_eval=0.0, seed=3,
     )
-    sim = BatchedGossipSimulator(cfg, LogRegSpec(d_in=57, n_classes=2), data)
+    sim = BatchedGossipSimulator(
+        cfg, LogRegSpec(d_in=57, n_classes=2), data, device=CPU
+    )
     sim.init_nodes()
     with RoundTimer(sim) as rt:
         sim.start(n_rounds=3)
@@ -2079,7 +2095,9 @@ def test_custom_delay_subclass_falls_back_to_python_scheduler():
         n_nodes=20, delta=10, protocol=AntiEntropyProtocol.PUSH,
         model_size=116, sampling_eval=0.0, seed=3, delay=JitterDelay(),
     )
-    sim = BatchedGossipSimulator(cfg, LogRegSpec(d_in=57, n_classes=2), data)
+    sim = BatchedGossipSimulator(
+        cfg, LogRegSpec(d_in=57, n_classes=2), data, device=CPU
+    )
     from gossipy_amd.engine import Scheduler
 
     assert type(sim.scheduler) is Scheduler  # python fallback
