@@ -109,7 +109,34 @@ def main():
         index.append(f"- [`{name}`](api/{fname})")
         print("wrote", fname)
     with open(os.path.join(ROOT, "docs", "API.md"), "w") as f:
-        f.write("\n".join(index) + "\n")
+        f.write("\n".join(index) + "\n" + COMPRESSION_NOTE)
+
+
+#: hand-written section of the index: which compression scheme runs on which
+#: engine model family (kept here so regenerating API.md preserves it)
+COMPRESSION_NOTE = """
+## Compressed gossip by model family
+
+Hegedus 2021's two compression schemes are spec fields plus a matching
+`EngineConfig` switch; both run on the torch oracle and, on one GPU, on the
+HIP kernels (per-tick path and whole-round executor), with the plain and the
+tokenized simulators. The multi-rank route is the model-agnostic one: for
+the MLP variants it is tested on the CPU oracle (two gloo ranks, bit-equal
+to one rank) and has not been run on more than one GPU.
+
+| scheme | spec | config | `LogRegSpec` | `MLPSpec` | other families |
+|---|---|---|---|---|---|
+| partitioned (`PartitionedTMH`) | `n_parts=P` | `EngineConfig(n_parts=P)` | yes | yes | `ValueError` |
+| sampled (`SamplingTMH`) | `sample_size=f` | `EngineConfig(sampled=True)` | yes | yes | `ValueError` |
+
+`n_parts` and `sample_size` are mutually exclusive, and `MLPSpec` rejects
+either together with `pass_through=True` (`ValueError`): PASS is an error
+for both handlers. Modes `MERGE_UPDATE`, `UPDATE` and `UPDATE_MERGE` are
+supported. Partitioned runs keep `[n_nodes, P]` ages. The MLP kernels hold
+the model row (two rows outside `MERGE_UPDATE`), one batch of activations
+and two gradient buffers in LDS and refuse shapes over 160 KiB per block;
+shrink `batch_size` or `hidden` when that check fires.
+"""
 
 
 if __name__ == "__main__":

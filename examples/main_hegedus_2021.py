@@ -5,6 +5,9 @@ Engine-first equivalent of the reference's main_hegedus_2021.py:43-60:
 PartitionedTMH logistic regression (4 partitions), 100 nodes, 20-regular
 topology, TokenizedGossipSimulator + RandomizedTokenAccount(C=20, A=10),
 constant utility. Synthetic spambase-shaped data.
+
+``--model mlp`` runs the same experiment with a partitioned MLP
+(``--hidden`` sets the hidden widths) instead of logistic regression.
 """
 
 import os
@@ -24,6 +27,7 @@ from gossipy_amd.engine import (
     DataArena,
     EngineConfig,
     LogRegSpec,
+    MLPSpec,
 )
 from gossipy_amd.flow_control import RandomizedTokenAccount
 from gossipy_amd.simul import SimulationReport
@@ -45,6 +49,11 @@ def main():
     ap.add_argument("--nodes", type=int, default=100)
     ap.add_argument("--rounds", type=int, default=100)
     ap.add_argument("--parts", type=int, default=4)
+    ap.add_argument("--model", choices=("logreg", "mlp"), default="logreg")
+    ap.add_argument(
+        "--hidden", type=int, nargs="+", default=[100],
+        help="hidden layer widths of the MLP (--model mlp)",
+    )
     args = ap.parse_args()
 
     device = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
@@ -57,19 +66,26 @@ def main():
         shards, device, global_eval=(X[idx[cut:]], y[idx[cut:]])
     )
 
+    if args.model == "mlp":
+        spec = MLPSpec(
+            d_in=d, n_classes=2, hidden=tuple(args.hidden), lr=0.1,
+            n_parts=args.parts,
+        )
+    else:
+        spec = LogRegSpec(d_in=d, n_classes=2, lr=0.1, n_parts=args.parts)
+
     indptr, indices = k_regular_csr(n, 20)
     cfg = EngineConfig(
         n_nodes=n,
         delta=100,
         protocol=AntiEntropyProtocol.PUSH,
-        model_size=2 * d + 2,
+        model_size=spec.D,
         sampling_eval=0.1,
         seed=42,
         n_parts=args.parts,
         peers_indptr=indptr,
         peers_indices=indices,
     )
-    spec = LogRegSpec(d_in=d, n_classes=2, lr=0.1, n_parts=args.parts)
     sim = BatchedTokenizedGossipSimulator(
         cfg,
         spec,

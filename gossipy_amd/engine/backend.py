@@ -77,15 +77,28 @@ class TorchBackend:
     name = "torch"
 
     def __init__(self):
-        #: per-spec partition tensors: id(spec) -> (perm, ptr, arena_part)
+        #: partition tensors by cover value (see _part_key) ->
+        #: (perm, ptr, arena_part)
         self._part_cache = {}
         #: pinned staging buffers for the pipelined eval fetch, per shape
         self._eval_bufs = {}
 
+    @staticmethod
+    def _part_key(spec):
+        """Everything the partition cover depends on. Keyed by value, not
+        ``id(spec)``: a recycled id could hand a spec of another family or
+        shape a perm table of the wrong length."""
+        return (
+            spec.family,
+            spec.D,
+            spec.n_parts,
+            tuple(tuple(int(v) for v in t) for t in spec._arena_layers()),
+        )
+
     def _part(self, spec, device):
         """(perm[D], ptr[P+1], arena_part[D]) on ``device`` for a
         partitioned spec (cached)."""
-        key = (id(spec), str(device))
+        key = (self._part_key(spec), str(device))
         hit = self._part_cache.get(key)
         if hit is None:
             perm = torch.from_numpy(spec.part_perm().astype(np.int64)).to(device)
@@ -341,6 +354,14 @@ class TorchBackend:
         _adjust_gradient, gossipy/model/handler.py:503-520): the whole age
         vector is incremented once per batch, and each parameter's gradient
         is divided by the age of its partition before the SGD step."""
+        if spec.family == "mlp":
+            self._update_part_mlp(params, ages, data, spec, nodes)
+            return
+        if spec.family != "logreg":
+            raise ValueError(
+                f"partitioned gossip is not implemented for family"
+                f" {spec.family!r}"
+            )
         d, k = spec.d_in, spec.n_classes
         _, _, apart = self._part(spec, params.device)
         for idx in nodes.tolist():
@@ -366,6 +387,51 @@ class TorchBackend:
                     g = torch.empty_like(row)
                     g[: k * d] = (dz.t() @ xb).reshape(-1)
                     g[k * d :] = dz.sum(0)
+                    g /= ages[idx].float()[apart]
+                    if spec.weight_decay:
+                        g += spec.weight_decay * row
+                    row -= spec.lr * g
+
+    def _update_part_mlp(self, params, ages, data, spec, nodes) -> None:
+        """MLP twin of the partitioned local step: forward/backward exactly
+        as :meth:`_update_mlp` (dX from the pre-update W), then the full
+        flat gradient is age-rescaled, weight-decayed and applied at once."""
+        offs = spec.layer_offsets()
+        _, _, apart = self._part(spec, params.device)
+        for idx in nodes.tolist():
+            c = int(data.counts[idx])
+            if c == 0:
+                continue
+            x = data.x[idx, :c]
+            y = data.y[idx, :c].long()
+            row = params[idx]
+            layers = [
+                (row[w_off:b_off].view(fout, fin), row[b_off : b_off + fout])
+                for (w_off, b_off, fin, fout) in offs
+            ]
+            bs = c if spec.batch_size == 0 else spec.batch_size
+            for _ in range(max(1, spec.local_epochs)):
+                for s in range(0, c, bs):
+                    xb, yb = x[s : s + bs], y[s : s + bs]
+                    m = xb.shape[0]
+                    ages[idx] += 1
+                    acts = [xb]
+                    h = xb
+                    for li, (W, b) in enumerate(layers):
+                        h = h @ W.t() + b
+                        if li < len(layers) - 1:
+                            h = torch.relu(h)
+                        acts.append(h)
+                    p = torch.softmax(acts[-1], dim=1)
+                    p[torch.arange(m), yb] -= 1.0
+                    dh = p / m
+                    g = torch.empty_like(row)
+                    for li in reversed(range(len(layers))):
+                        w_off, b_off, fin, fout = offs[li]
+                        g[w_off:b_off] = (dh.t() @ acts[li]).reshape(-1)
+                        g[b_off : b_off + fout] = dh.sum(0)
+                        if li > 0:
+                            dh = (dh @ layers[li][0]) * (acts[li] > 0).float()
                     g /= ages[idx].float()[apart]
                     if spec.weight_decay:
                         g += spec.weight_decay * row
@@ -1608,13 +1674,25 @@ class HIPBackend(TorchBackend):
 
     def _part_dev(self, spec, dev):
         """(perm, ptr, arena_part) as int32 device tensors (cached)."""
-        key = ("dev32", id(spec), str(dev))
+        key = ("dev32", self._part_key(spec), str(dev))
         hit = self._part_cache.get(key)
         if hit is None:
             perm = torch.from_numpy(spec.part_perm()).to(dev)
             ptr = torch.from_numpy(spec.part_ptr()).to(dev)
             apart = torch.from_numpy(spec.arena_part()).to(dev)
             hit = (perm, ptr, apart)
+            self._part_cache[key] = hit
+        return hit
+
+    def _mlp_layout(self, spec, dev):
+        """``[n_layers*4]`` int32 device tensor of (w_off, b_off, in, out),
+        cached by value next to the perm tables (it depends on the layer
+        shapes alone)."""
+        flat = tuple(int(x) for t in spec.layer_offsets() for x in t)
+        key = ("mlp_layout", flat, str(dev))
+        hit = self._part_cache.get(key)
+        if hit is None:
+            hit = torch.tensor(flat, dtype=torch.int32, device=dev)
             self._part_cache[key] = hit
         return hit
 
@@ -1634,8 +1712,40 @@ class HIPBackend(TorchBackend):
         else:
             slots, slot_ages = pool.slots, pool.slot_ages
         mode = _MODE_ID[spec.mode]
-        if getattr(spec, "n_parts", 0) > 0:
-            assert spec.family == "logreg", "partitioned HIP path: logreg only"
+        if getattr(spec, "n_parts", 0) > 0 and spec.family == "mlp":
+            perm, ptr, apart = self._part_dev(spec, dev)
+            self.ext.tick_mlp_part(
+                state.params,
+                state.ages,
+                slots,
+                slot_ages,
+                nodes,
+                recv_ptr,
+                del_slots,
+                reply_slots,
+                del_pids,
+                data.x,
+                data.y,
+                data.counts,
+                self._mlp_layout(spec, dev),
+                len(spec.layer_offsets()),
+                perm,
+                ptr,
+                apart,
+                spec.n_parts,
+                spec.lr,
+                spec.weight_decay,
+                max(1, spec.local_epochs),
+                spec.batch_size,
+                mode,
+                bool(update_only),
+            )
+        elif getattr(spec, "n_parts", 0) > 0:
+            if spec.family != "logreg":
+                raise ValueError(
+                    f"partitioned gossip has no HIP path for family"
+                    f" {spec.family!r}"
+                )
             perm, ptr, apart = self._part_dev(spec, dev)
             self.ext.tick_logreg_part(
                 state.params,
@@ -1712,8 +1822,36 @@ class HIPBackend(TorchBackend):
                 mode,
                 bool(update_only),
             )
+        elif getattr(spec, "sample_size", 0) > 0 and spec.family == "mlp":
+            self.ext.tick_mlp_samp(
+                state.params,
+                state.ages,
+                slots,
+                slot_ages,
+                nodes,
+                recv_ptr,
+                del_slots,
+                reply_slots,
+                del_pids,
+                data.x,
+                data.y,
+                data.counts,
+                self._mlp_layout(spec, dev),
+                len(spec.layer_offsets()),
+                spec.samp_count(),
+                spec.lr,
+                spec.weight_decay,
+                max(1, spec.local_epochs),
+                spec.batch_size,
+                mode,
+                bool(update_only),
+            )
         elif getattr(spec, "sample_size", 0) > 0:
-            assert spec.family == "logreg", "sampled HIP path: logreg only"
+            if spec.family != "logreg":
+                raise ValueError(
+                    f"sampled gossip has no HIP path for family"
+                    f" {spec.family!r}"
+                )
             self.ext.tick_logreg_samp(
                 state.params,
                 state.ages,

@@ -183,6 +183,11 @@ class MLPSpec(_PartitionMixin):
 
     Parameter row layout: per layer ``W_i`` (out_i * in_i, row-major) then
     ``b_i`` (out_i), layers packed in order.
+    ``n_parts > 0`` switches the family to partitioned gossip and
+    ``sample_size > 0`` to sampled gossip, with the semantics documented on
+    :class:`LogRegSpec`; the two are mutually exclusive, and neither
+    combines with ``pass_through`` (PASS is an error for both handlers,
+    gossipy/model/handler.py:449-452, 491-494).
     """
 
     d_in: int
@@ -195,8 +200,27 @@ class MLPSpec(_PartitionMixin):
     mode: CreateModelMode = CreateModelMode.MERGE_UPDATE
     n_parts: int = 0
     pass_through: bool = False
+    #: >0 = sampled gossip (see :class:`LogRegSpec`); last field so
+    #: positional construction of older call sites is unchanged
+    sample_size: float = 0.0
 
     family = "mlp"
+
+    def __post_init__(self):
+        if self.n_parts > 0 and self.sample_size > 0:
+            raise ValueError(
+                "MLPSpec: n_parts and sample_size are mutually exclusive"
+            )
+        if self.pass_through and (self.n_parts > 0 or self.sample_size > 0):
+            raise ValueError(
+                "MLPSpec: pass_through cannot be combined with n_parts or"
+                " sample_size (Mode PASS is not allowed for partitioned or"
+                " sampled models)"
+            )
+
+    def samp_count(self) -> int:
+        """Coordinates per sampled merge (gossipy/model/sampling.py:57)."""
+        return max(1, int(round(self.sample_size * self.D)))
 
     def _arena_layers(self):
         return self.layer_offsets()

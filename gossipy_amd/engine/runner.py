@@ -809,7 +809,10 @@ class BatchedGossipSimulator(SimulationEventSender):
             self.world == 1
             and getattr(self.backend, "ext", None) is not None
             and self.spec.family in ("logreg", "pegasos", "adaline", "mlp", "mf")
-            and (self.spec.family == "logreg" or getattr(self.spec, "n_parts", 0) == 0)
+            and (
+                self.spec.family in ("logreg", "mlp")
+                or getattr(self.spec, "n_parts", 0) == 0
+            )
             and not getattr(self.spec, "pass_through", False)
             and (self.spec.family != "mf" or self.spec.mode == CreateModelMode.MERGE_UPDATE)
         )
@@ -1318,7 +1321,39 @@ class BatchedGossipSimulator(SimulationEventSender):
                             "falling back to the stream executor", e)
                 self._coop_enabled = False
 
-        if getattr(spec, "sample_size", 0) > 0:
+        # executor by (family, n_parts, sample_size)
+        n_parts = getattr(spec, "n_parts", 0)
+        sample_size = getattr(spec, "sample_size", 0)
+        if spec.family == "mlp" and (n_parts > 0 or sample_size > 0):
+            # same del_pids/rep_pids positions as the logreg variants
+            c = list(common)
+            c.insert(12, views["del_pids"])   # after reply_slots
+            c.insert(20, views["rep_pids"])   # after rep_slots
+            c += [
+                self.backend._mlp_layout(spec, dev),
+                len(spec.layer_offsets()),
+            ]
+            tail = (
+                spec.lr,
+                spec.weight_decay,
+                max(1, spec.local_epochs),
+                spec.batch_size,
+                _MODE_ID[spec.mode],
+                views["rep_reply_slots"],
+            )
+            if n_parts > 0:
+                perm, pptr, apart = self.backend._part_dev(spec, dev)
+                ext.run_round_mlp_part(
+                    *c, perm, pptr, apart, spec.n_parts, *tail
+                )
+            else:
+                ext.run_round_mlp_samp(*c, spec.samp_count(), *tail)
+        elif sample_size > 0:
+            if spec.family != "logreg":
+                raise ValueError(
+                    f"sampled gossip has no round executor for family"
+                    f" {spec.family!r}"
+                )
             c = list(common)
             c.insert(12, views["del_pids"])   # sample seeds ride the pid slot
             c.insert(20, views["rep_pids"])

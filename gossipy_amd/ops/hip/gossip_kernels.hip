@@ -22,6 +22,9 @@
 //                           one wave per node, weights in registers.
 //   tick_mlp_kernel       — K3/K4 generalized: fused MLP fwd/bwd/SGD
 //                           (gossipy/model/nn.py:91-99).
+//   tick_mlp_comp_kernel  — the MLP tick under partitioned / sampled
+//                           gossip (gossipy/model/handler.py:426-525),
+//                           same SGD body, templated on the merge policy.
 //
 // Models are tiny (57x2 logreg ... few-hundred-wide MLPs); per-launch work
 // is launch-latency bound, so kernels are built to let ONE launch cover all
@@ -1155,8 +1158,17 @@ DEV_INLINE f32x4_t mfma_kloop(int Kdim, LoadA la, LoadB lb)
     return acc;
 }
 
+// PART = partitioned gossip (PartitionedTMH._local_step + _adjust_gradient,
+// gossipy/model/handler.py:503-520): the age is the LDS vector agev[P],
+// bumped whole before each minibatch step, and every parameter's gradient
+// is divided by the age of its partition (apart: arena offset -> partition
+// id) before weight decay. The plain instantiation ignores agev/apart/P and
+// compiles to the scalar-age code unchanged.
+template <bool PART>
 DEV_INLINE void mlp_update(const MlpArgs& a, int node, float* W,
-                           float* act, float* grad, int& age)
+                           float* act, float* grad, int& age,
+                           int* agev = nullptr, const int* apart = nullptr,
+                           int P = 0)
 {
     int tid = threadIdx.x;
     int c = a.counts[node];
@@ -1177,6 +1189,12 @@ DEV_INLINE void mlp_update(const MlpArgs& a, int node, float* W,
             float* in = act;
             for (int e = tid; e < m * a.d_in; e += blockDim.x)
                 in[e] = Xn[(long)s0 * a.d_in + e];
+            if constexpr (PART) {
+                // self.n_updates += 1 happens before the step
+                // (handler.py:506); first read is the dW epilogue, behind
+                // the barriers below
+                for (int p = tid; p < P; p += blockDim.x) agev[p] += 1;
+            }
             __syncthreads();
             // ---- forward: H = X · Wᵀ + b on MFMA
             float* cur = in;
@@ -1278,6 +1296,18 @@ DEV_INLINE void mlp_update(const MlpArgs& a, int node, float* W,
                     int o16 = (fout + 15) >> 4, q16 = (fin + 15) >> 4;
                     for (int tile = wave; tile < o16 * q16; tile += nwaves) {
                         int tr = (tile / q16) << 4, tc = (tile % q16) << 4;
+                        // partition ids of this lane's four outputs: the
+                        // L2 loads issue ahead of the MFMA chain, which
+                        // hides their latency from the epilogue
+                        int pe[4];
+                        if constexpr (PART) {
+                            for (int r = 0; r < 4; ++r) {
+                                int row = tr + (fk << 2) + r, col = tc + fr;
+                                pe[r] = (row < fout && col < fin)
+                                            ? apart[w_off + row * fin + col]
+                                            : 0;
+                            }
+                        }
                         f32x4_t acc = mfma_kloop(
                             m,
                             [&](int k0) {
@@ -1297,6 +1327,8 @@ DEV_INLINE void mlp_update(const MlpArgs& a, int node, float* W,
                             if (row < fout && col < fin) {
                                 float g = acc[r];
                                 int e = row * fin + col;
+                                if constexpr (PART)  // _adjust_gradient
+                                    g /= (float)agev[pe[r]];
                                 if (a.wd != 0.f) g += a.wd * W[w_off + e];
                                 W[w_off + e] -= a.lr * g;
                             }
@@ -1306,12 +1338,18 @@ DEV_INLINE void mlp_update(const MlpArgs& a, int node, float* W,
                 for (int e = tid; e < fout; e += blockDim.x) {
                     float g = 0.f;
                     for (int s = 0; s < m; ++s) g += gcur[s * fout + e];
+                    if constexpr (PART) {
+                        // the rescaled flat gradient is decayed as a whole
+                        // (biases included), unlike the plain step
+                        g /= (float)agev[apart[b_off + e]];
+                        if (a.wd != 0.f) g += a.wd * W[b_off + e];
+                    }
                     W[b_off + e] -= a.lr * g;
                 }
                 __syncthreads();
                 float* tmp = gcur; gcur = gnext; gnext = tmp;
             }
-            age += 1;
+            if constexpr (!PART) age += 1;
         }
     }
 }
@@ -1344,7 +1382,7 @@ tick_mlp_kernel(MlpArgs a)
     int age = a.ages[node];
 
     if (a.update_only) {
-        mlp_update(a, node, W, act, grad, age);
+        mlp_update<false>(a, node, W, act, grad, age);
     } else {
         for (int j = a.ptr[i]; j < a.ptr[i + 1]; ++j) {
             int slot = a.dslots[j];
@@ -1356,18 +1394,18 @@ tick_mlp_kernel(MlpArgs a)
                     W[e] = 0.5f * (W[e] + srow[e]);
                 age = max(age, sage);
                 __syncthreads();
-                mlp_update(a, node, W, act, grad, age);
+                mlp_update<false>(a, node, W, act, grad, age);
             } else if (md == MODE_UPDATE) {
                 for (int e = tid; e < a.D; e += blockDim.x) W[e] = srow[e];
                 age = sage;
                 __syncthreads();
-                mlp_update(a, node, W, act, grad, age);
+                mlp_update<false>(a, node, W, act, grad, age);
             } else if (md == MODE_UPDATE_MERGE) {
-                mlp_update(a, node, W, act, grad, age);
+                mlp_update<false>(a, node, W, act, grad, age);
                 for (int e = tid; e < a.D; e += blockDim.x) W2[e] = srow[e];
                 __syncthreads();
                 int age2 = sage;
-                mlp_update(a, node, W2, act, grad, age2);
+                mlp_update<false>(a, node, W2, act, grad, age2);
                 for (int e = tid; e < a.D; e += blockDim.x)
                     W[e] = 0.5f * (W[e] + W2[e]);
                 age = max(age, age2);
@@ -1390,6 +1428,169 @@ tick_mlp_kernel(MlpArgs a)
     for (int e = tid; e < a.D; e += blockDim.x)
         a.params[(long)node * a.D + e] = W[e];
     if (tid == 0) a.ages[node] = age;
+}
+
+// ---------------------------------------------------------------------------
+// compressed MLP ticks: partitioned (PartitionedTMH) and sampled
+// (SamplingTMH) delivery on the tick_mlp_kernel structure — block per
+// receiver, model row LDS-resident, SGD through mlp_update's MFMA stages.
+//
+// Parity: delivery semantics are those of logreg_part_process_node and
+// tick_logreg_samp_kernel above (gossipy/model/handler.py:426-525). PASS is
+// rejected host-side for both.
+// ---------------------------------------------------------------------------
+
+struct MlpCompArgs {
+    MlpArgs m;         // dmodes unused
+    const int* dpids;  // per delivery: partition id (PART) / sample seed
+    const int* perm;   // [D]   partition-ordered -> arena offset   (PART)
+    const int* pptr;   // [P+1]                                     (PART)
+    const int* apart;  // [D]   arena offset -> partition id        (PART)
+    int P;             // partitions; ages / slot_ages are [*, P]   (PART)
+    int samp_c;        // coordinates per sampled merge
+    //: sampled: the pre-merge copy lives in the act/grad scratch (idle
+    //: between SGD steps) instead of a slab of its own — decided host-side
+    int w3_alias;
+};
+
+// Age-weighted merge of partition `pid` of src into W (handler.py:497-501;
+// weights (0,0) -> (1/2,1/2)); that partition's age becomes the max. src /
+// src_ages may point to LDS (trained received model) or HBM (slot row).
+DEV_INLINE void mlp_part_merge(const MlpCompArgs& c, float* W, int* agev,
+                               const float* src, const int* src_ages, int pid)
+{
+    int tid = threadIdx.x;
+    int w1 = agev[pid], w2 = src_ages[pid];
+    float m1, m2;
+    if (w1 == 0 && w2 == 0) { m1 = 0.5f; m2 = 0.5f; }
+    else {
+        float s = (float)(w1 + w2);
+        m1 = (float)w1 / s;
+        m2 = (float)w2 / s;
+    }
+    __syncthreads();
+    for (int e = c.pptr[pid] + tid; e < c.pptr[pid + 1]; e += blockDim.x) {
+        int i = c.perm[e];
+        W[i] = m1 * W[i] + m2 * src[i];
+    }
+    if (tid == 0) agev[pid] = max(w1, w2);
+    __syncthreads();
+}
+
+// Sampled mean merge: W[i] = (W[i] + src[i]) / 2 over the index stream
+// splitmix64(seed + q) % D, q < samp_c (engine/rng.py sample_indices). W3
+// holds the pre-merge W so duplicate indices all read the ORIGINAL value
+// (torch advanced-index assignment semantics); duplicates then store the
+// same value, so their order does not matter.
+DEV_INLINE void mlp_samp_merge(const MlpCompArgs& c, float* W, float* W3,
+                               const float* src, int seed)
+{
+    int tid = threadIdx.x;
+    int D = c.m.D;
+    for (int e = tid; e < D; e += blockDim.x) W3[e] = W[e];
+    __syncthreads();
+    for (int q = tid; q < c.samp_c; q += blockDim.x) {
+        int i = (int)(splitmix64_dev((unsigned long long)seed +
+                                     (unsigned long long)q) %
+                      (unsigned long long)D);
+        W[i] = 0.5f * (W3[i] + src[i]);
+    }
+    __syncthreads();
+}
+
+template <bool PART>
+__global__ void __launch_bounds__(512)
+tick_mlp_comp_kernel(MlpCompArgs c)
+{
+    const MlpArgs& a = c.m;
+    int i = blockIdx.x;
+    int node = a.nodes[i];
+    int tid = threadIdx.x;
+    extern __shared__ float sm[];
+    // LDS (host computes the same sum): W | W2 unless MERGE_UPDATE | W3 when
+    // sampled and not aliased | act | 2 grad buffers | agev, agev2 (PART)
+    float* W = sm;
+    bool has_w2 = (a.mode != MODE_MERGE_UPDATE);
+    float* W2 = has_w2 ? W + a.D : nullptr;
+    float* next = W + (has_w2 ? 2 : 1) * (size_t)a.D;
+    float* W3 = nullptr;
+    if (!PART && !c.w3_alias) { W3 = next; next += a.D; }
+    float* act = next;
+    int bsmax = (a.bs == 0) ? a.Smax : min(a.bs, a.Smax);
+    int act_total = 0;
+    for (int l = 0; l < a.n_layers; ++l) act_total += a.layout[4 * l + 3];
+    float* grad = act + bsmax * (a.d_in + act_total);
+    if (!PART && c.w3_alias) W3 = act;
+    int* agev = (int*)(grad + 2 * bsmax * a.act_max);  // P     (PART)
+    int* agev2 = agev + c.P;                            // P     (PART)
+    const int P = PART ? c.P : 0;
+
+    for (int e = tid; e < a.D; e += blockDim.x)
+        W[e] = a.params[(long)node * a.D + e];
+    for (int p = tid; p < P; p += blockDim.x)
+        agev[p] = a.ages[(long)node * P + p];
+    __syncthreads();
+    int age = PART ? 0 : a.ages[node];
+
+    if (a.update_only) {
+        mlp_update<PART>(a, node, W, act, grad, age, agev, c.apart, P);
+    } else {
+        for (int j = a.ptr[i]; j < a.ptr[i + 1]; ++j) {
+            int slot = a.dslots[j];
+            int pid = c.dpids ? c.dpids[j] : 0;  // partition id / seed
+            const float* srow = a.slots + (long)slot * a.D;
+            if (a.mode == MODE_MERGE_UPDATE) {
+                if constexpr (PART)
+                    mlp_part_merge(c, W, agev, srow,
+                                   a.slot_ages + (long)slot * P, pid);
+                else
+                    mlp_samp_merge(c, W, W3, srow, pid);
+                mlp_update<PART>(a, node, W, act, grad, age, agev, c.apart, P);
+            } else {
+                // UPDATE: train the received model, merge its partition /
+                // sample into self (handler.py:440-442, 481-483).
+                // UPDATE_MERGE: self-update first (handler.py:445-448,
+                // 487-490).
+                if (a.mode == MODE_UPDATE_MERGE)
+                    mlp_update<PART>(a, node, W, act, grad, age, agev,
+                                     c.apart, P);
+                for (int e = tid; e < a.D; e += blockDim.x) W2[e] = srow[e];
+                for (int p = tid; p < P; p += blockDim.x)
+                    agev2[p] = a.slot_ages[(long)slot * P + p];
+                __syncthreads();
+                // sampled: the received model's scalar age is trained and
+                // dropped — ages are never merged (handler.py:431-433)
+                int age2 = 0;
+                mlp_update<PART>(a, node, W2, act, grad, age2, agev2,
+                                 c.apart, P);
+                if constexpr (PART)
+                    mlp_part_merge(c, W, agev, W2, agev2, pid);
+                else
+                    mlp_samp_merge(c, W, W3, W2, pid);
+            }
+            int rs = a.rslots ? a.rslots[j] : -1;
+            if (rs >= 0) {
+                for (int e = tid; e < a.D; e += blockDim.x)
+                    a.slots[(long)rs * a.D + e] = W[e];
+                if constexpr (PART) {
+                    for (int p = tid; p < P; p += blockDim.x)
+                        a.slot_ages[(long)rs * P + p] = agev[p];
+                } else {
+                    if (tid == 0) a.slot_ages[rs] = age;
+                }
+                __syncthreads();
+            }
+        }
+    }
+    __syncthreads();
+    for (int e = tid; e < a.D; e += blockDim.x)
+        a.params[(long)node * a.D + e] = W[e];
+    if constexpr (PART) {
+        for (int p = tid; p < P; p += blockDim.x)
+            a.ages[(long)node * P + p] = agev[p];
+    } else {
+        if (tid == 0) a.ages[node] = age;
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -2133,6 +2334,162 @@ void tick_mlp(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
                        current_stream(), a);
 }
 
+// Launch geometry of the compressed MLP kernels, shared by the tick and
+// whole-round entry points.
+struct MlpCompLaunch {
+    MlpCompArgs c;
+    size_t smem;
+    int threads;
+};
+
+// Fills every per-spec field (pointers to the per-call event arrays are
+// left to the caller) and checks the per-mode LDS budget: W, +W2 unless
+// MERGE_UPDATE, +the sampled pre-merge copy unless it fits the act/grad
+// scratch, activations, two grad buffers, 2*P age ints when partitioned.
+static MlpCompLaunch mlp_comp_setup(
+    bool part, torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
+    torch::Tensor slot_ages, torch::Tensor X, torch::Tensor Y,
+    torch::Tensor counts, torch::Tensor layout, int64_t n_layers,
+    int64_t n_parts, int64_t samp_c, double lr, double wd, int64_t epochs,
+    int64_t bs, int64_t mode)
+{
+    const char* what = part ? "partitioned" : "sampled";
+    CHECK_DEV(params); CHECK_DEV(slots); CHECK_DEV(X); CHECK_DEV(Y);
+    CHECK_DEV(layout);
+    TORCH_CHECK(mode != MODE_PASS, "Mode PASS not allowed for ", what,
+                " models.");
+    TORCH_CHECK(n_layers >= 1 && layout.numel() == 4 * n_layers,
+                "mlp layout must hold n_layers x (w_off, b_off, in, out)");
+    MlpCompLaunch L;
+    MlpCompArgs& c = L.c;
+    MlpArgs& a = c.m;
+    a.params = params.data_ptr<float>(); a.ages = ages.data_ptr<int>();
+    a.slots = slots.data_ptr<float>(); a.slot_ages = slot_ages.data_ptr<int>();
+    a.nodes = nullptr; a.ptr = nullptr; a.dslots = nullptr; a.rslots = nullptr;
+    a.dmodes = nullptr;
+    a.X = X.data_ptr<float>(); a.Y = Y.data_ptr<float>();
+    a.counts = counts.data_ptr<int>();
+    a.layout = layout.data_ptr<int>();
+    a.n_layers = n_layers; a.Smax = X.size(1); a.D = params.size(1);
+    a.lr = lr; a.wd = wd; a.epochs = epochs; a.bs = bs; a.mode = mode;
+    a.update_only = 0;
+    c.dpids = nullptr; c.perm = nullptr; c.pptr = nullptr; c.apart = nullptr;
+    c.P = part ? (int)n_parts : 0;
+    c.samp_c = part ? 0 : (int)samp_c;
+    c.w3_alias = 0;
+    if (part) {
+        TORCH_CHECK(n_parts >= 1, "n_parts must be positive");
+        TORCH_CHECK(ages.numel() == ages.size(0) * n_parts &&
+                    slot_ages.numel() == slot_ages.size(0) * n_parts,
+                    "partitioned mlp: ages and slot_ages must be [*, n_parts]");
+    } else {
+        TORCH_CHECK(samp_c >= 1, "samp_c must be positive");
+    }
+    auto lay = layout.cpu();
+    const int* Lh = lay.data_ptr<int>();
+    int act_sum = 0, act_max = Lh[2];
+    for (int l = 0; l < n_layers; ++l) {
+        act_sum += Lh[4 * l + 3];
+        act_max = std::max(act_max, Lh[4 * l + 3]);
+        act_max = std::max(act_max, Lh[4 * l + 2]);
+    }
+    a.act_max = act_max;
+    a.d_in = Lh[2];
+    int bsmax = (bs == 0) ? a.Smax : std::min<int>(bs, a.Smax);
+    size_t scratch = (size_t)bsmax * (a.d_in + act_sum) +
+                     2 * (size_t)bsmax * act_max;
+    size_t w_slabs = (mode == MODE_MERGE_UPDATE) ? 1 : 2;
+    if (!part) {
+        c.w3_alias = (scratch >= (size_t)a.D) ? 1 : 0;
+        if (!c.w3_alias) w_slabs += 1;
+    }
+    L.smem = sizeof(float) * (w_slabs * (size_t)a.D + scratch) +
+             sizeof(int) * 2 * (size_t)c.P;
+    TORCH_CHECK(L.smem <= 160 * 1024, what, " mlp LDS budget exceeded (",
+                L.smem, " B > 163840 B); shrink batch_size/hidden, or use"
+                " MERGE_UPDATE (the other modes hold a second model slab)");
+    // block size policy as in tick_mlp: 8 waves when any GEMM stage has
+    // >= 8 MFMA tiles, else 4
+    int max_tiles = 0;
+    int m16 = (bsmax + 15) >> 4;
+    for (int l = 0; l < n_layers; ++l) {
+        int fin16 = (Lh[4 * l + 2] + 15) >> 4;
+        int fout16 = (Lh[4 * l + 3] + 15) >> 4;
+        max_tiles = std::max(max_tiles, m16 * fout16);   // forward
+        max_tiles = std::max(max_tiles, m16 * fin16);    // dX
+        max_tiles = std::max(max_tiles, fout16 * fin16); // dW
+    }
+    L.threads = (max_tiles >= 8) ? 512 : 256;
+    return L;
+}
+
+static void mlp_comp_launch(bool part, const MlpCompLaunch& L, int n,
+                            hipStream_t s)
+{
+    if (part)
+        hipLaunchKernelGGL(tick_mlp_comp_kernel<true>, dim3(n),
+                           dim3(L.threads), L.smem, s, L.c);
+    else
+        hipLaunchKernelGGL(tick_mlp_comp_kernel<false>, dim3(n),
+                           dim3(L.threads), L.smem, s, L.c);
+}
+
+static void tick_mlp_comp(
+    bool part, torch::Tensor nodes, torch::Tensor recv_ptr,
+    torch::Tensor del_slots, torch::Tensor reply_slots, torch::Tensor del_pids,
+    bool update_only, MlpCompLaunch& L)
+{
+    int n = nodes.size(0);
+    if (n == 0) return;
+    CHECK_DEV(nodes); CHECK_DEV(recv_ptr);
+    L.c.m.nodes = nodes.data_ptr<int>(); L.c.m.ptr = recv_ptr.data_ptr<int>();
+    L.c.m.dslots = del_slots.numel() ? del_slots.data_ptr<int>() : nullptr;
+    L.c.m.rslots = reply_slots.numel() ? reply_slots.data_ptr<int>() : nullptr;
+    L.c.dpids = del_pids.numel() ? del_pids.data_ptr<int>() : nullptr;
+    L.c.m.update_only = update_only;
+    mlp_comp_launch(part, L, n, current_stream());
+}
+
+void tick_mlp_part(
+    torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
+    torch::Tensor slot_ages, torch::Tensor nodes, torch::Tensor recv_ptr,
+    torch::Tensor del_slots, torch::Tensor reply_slots, torch::Tensor del_pids,
+    torch::Tensor X, torch::Tensor Y, torch::Tensor counts,
+    torch::Tensor layout, int64_t n_layers,
+    torch::Tensor perm, torch::Tensor pptr, torch::Tensor apart,
+    int64_t n_parts, double lr, double wd, int64_t epochs, int64_t bs,
+    int64_t mode, bool update_only)
+{
+    CHECK_DEV(perm); CHECK_DEV(pptr); CHECK_DEV(apart);
+    MlpCompLaunch L = mlp_comp_setup(
+        true, params, ages, slots, slot_ages, X, Y, counts, layout, n_layers,
+        n_parts, 0, lr, wd, epochs, bs, mode);
+    TORCH_CHECK(perm.numel() == params.size(1) &&
+                apart.numel() == params.size(1) &&
+                pptr.numel() == n_parts + 1,
+                "partition tables do not match the model row");
+    L.c.perm = perm.data_ptr<int>(); L.c.pptr = pptr.data_ptr<int>();
+    L.c.apart = apart.data_ptr<int>();
+    tick_mlp_comp(true, nodes, recv_ptr, del_slots, reply_slots, del_pids,
+                  update_only, L);
+}
+
+void tick_mlp_samp(
+    torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
+    torch::Tensor slot_ages, torch::Tensor nodes, torch::Tensor recv_ptr,
+    torch::Tensor del_slots, torch::Tensor reply_slots, torch::Tensor del_seeds,
+    torch::Tensor X, torch::Tensor Y, torch::Tensor counts,
+    torch::Tensor layout, int64_t n_layers, int64_t samp_c,
+    double lr, double wd, int64_t epochs, int64_t bs, int64_t mode,
+    bool update_only)
+{
+    MlpCompLaunch L = mlp_comp_setup(
+        false, params, ages, slots, slot_ages, X, Y, counts, layout, n_layers,
+        0, samp_c, lr, wd, epochs, bs, mode);
+    tick_mlp_comp(false, nodes, recv_ptr, del_slots, reply_slots, del_seeds,
+                  update_only, L);
+}
+
 // ---------------------------------------------------------------------------
 // round executors: the C++ loop over one round's ticks. All event arrays
 // arrive on-device ONCE per round; tick boundary pointers stay host-side.
@@ -2682,6 +3039,113 @@ void run_round_mlp(
     }
 }
 
+// The tick loop of run_round_mlp for the compressed kernels: del_pids /
+// rep_pids carry the partition ids (partitioned) or sample seeds (sampled),
+// and snapshots copy A ages per row.
+static void run_round_mlp_comp(bool part, MlpCompLaunch& L,
+                               const RoundArrays& r, const int* d_pids,
+                               const int* r_pids, const int* rep_rr, int A)
+{
+    hipStream_t s = current_stream();
+    MlpArgs& a = L.c.m;
+    for (int t = 0; t < r.delta; ++t) {
+        int s0 = r.snap_tptr[t], s1 = r.snap_tptr[t + 1];
+        if (s1 > s0)
+            launch_snap(a.params, a.ages, a.slots, a.slot_ages,
+                        r.snap_nodes + s0, r.snap_slots + s0, s1 - s0, a.D, s,
+                        A);
+        int r0 = r.recv_tptr[t], r1 = r.recv_tptr[t + 1];
+        if (r1 > r0) {
+            a.nodes = r.recv_nodes + r0;
+            a.ptr = r.recv_nptr + r0;
+            a.dslots = r.del_slots;
+            a.rslots = r.reply_slots;
+            L.c.dpids = d_pids;
+            mlp_comp_launch(part, L, r1 - r0, s);
+        }
+        int p0 = r.pull_tptr[t], p1 = r.pull_tptr[t + 1];
+        if (p1 > p0)
+            launch_snap(a.params, a.ages, a.slots, a.slot_ages,
+                        r.pull_nodes + p0, r.pull_slots + p0, p1 - p0, a.D, s,
+                        A);
+        int q0 = r.rep_tptr[t], q1 = r.rep_tptr[t + 1];
+        if (q1 > q0) {
+            a.nodes = r.rep_nodes + q0;
+            a.ptr = r.rep_nptr + q0;
+            a.dslots = r.rep_slots;
+            a.rslots = rep_rr;
+            L.c.dpids = r_pids;
+            mlp_comp_launch(part, L, q1 - q0, s);
+        }
+    }
+}
+
+void run_round_mlp_part(
+    torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
+    torch::Tensor slot_ages,
+    torch::Tensor snap_nodes, torch::Tensor snap_slots, torch::Tensor snap_tptr,
+    torch::Tensor recv_nodes, torch::Tensor recv_nptr, torch::Tensor recv_tptr,
+    torch::Tensor del_slots, torch::Tensor reply_slots, torch::Tensor del_pids,
+    torch::Tensor pull_nodes, torch::Tensor pull_slots, torch::Tensor pull_tptr,
+    torch::Tensor rep_nodes, torch::Tensor rep_nptr, torch::Tensor rep_tptr,
+    torch::Tensor rep_slots, torch::Tensor rep_pids,
+    torch::Tensor X, torch::Tensor Y, torch::Tensor counts,
+    torch::Tensor layout, int64_t n_layers,
+    torch::Tensor perm, torch::Tensor pptr, torch::Tensor apart,
+    int64_t n_parts, double lr, double wd, int64_t epochs, int64_t bs,
+    int64_t mode, torch::Tensor rep_reply_slots)
+{
+    CHECK_DEV(perm); CHECK_DEV(pptr); CHECK_DEV(apart);
+    MlpCompLaunch L = mlp_comp_setup(
+        true, params, ages, slots, slot_ages, X, Y, counts, layout, n_layers,
+        n_parts, 0, lr, wd, epochs, bs, mode);
+    TORCH_CHECK(perm.numel() == params.size(1) &&
+                apart.numel() == params.size(1) &&
+                pptr.numel() == n_parts + 1,
+                "partition tables do not match the model row");
+    L.c.perm = perm.data_ptr<int>(); L.c.pptr = pptr.data_ptr<int>();
+    L.c.apart = apart.data_ptr<int>();
+    RoundArrays r = unpack_round(snap_nodes, snap_slots, snap_tptr, recv_nodes,
+                                 recv_nptr, recv_tptr, del_slots, reply_slots,
+                                 pull_nodes, pull_slots, pull_tptr, rep_nodes,
+                                 rep_nptr, rep_tptr, rep_slots);
+    const int* d_pids = del_pids.numel() ? del_pids.data_ptr<int>() : nullptr;
+    const int* r_pids = rep_pids.numel() ? rep_pids.data_ptr<int>() : nullptr;
+    const int* rep_rr =
+        (rep_reply_slots.defined() && rep_reply_slots.numel())
+            ? rep_reply_slots.data_ptr<int>() : nullptr;
+    run_round_mlp_comp(true, L, r, d_pids, r_pids, rep_rr, (int)n_parts);
+}
+
+void run_round_mlp_samp(
+    torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
+    torch::Tensor slot_ages,
+    torch::Tensor snap_nodes, torch::Tensor snap_slots, torch::Tensor snap_tptr,
+    torch::Tensor recv_nodes, torch::Tensor recv_nptr, torch::Tensor recv_tptr,
+    torch::Tensor del_slots, torch::Tensor reply_slots, torch::Tensor del_pids,
+    torch::Tensor pull_nodes, torch::Tensor pull_slots, torch::Tensor pull_tptr,
+    torch::Tensor rep_nodes, torch::Tensor rep_nptr, torch::Tensor rep_tptr,
+    torch::Tensor rep_slots, torch::Tensor rep_pids,
+    torch::Tensor X, torch::Tensor Y, torch::Tensor counts,
+    torch::Tensor layout, int64_t n_layers, int64_t samp_c,
+    double lr, double wd, int64_t epochs, int64_t bs, int64_t mode,
+    torch::Tensor rep_reply_slots)
+{
+    MlpCompLaunch L = mlp_comp_setup(
+        false, params, ages, slots, slot_ages, X, Y, counts, layout, n_layers,
+        0, samp_c, lr, wd, epochs, bs, mode);
+    RoundArrays r = unpack_round(snap_nodes, snap_slots, snap_tptr, recv_nodes,
+                                 recv_nptr, recv_tptr, del_slots, reply_slots,
+                                 pull_nodes, pull_slots, pull_tptr, rep_nodes,
+                                 rep_nptr, rep_tptr, rep_slots);
+    const int* d_pids = del_pids.numel() ? del_pids.data_ptr<int>() : nullptr;
+    const int* r_pids = rep_pids.numel() ? rep_pids.data_ptr<int>() : nullptr;
+    const int* rep_rr =
+        (rep_reply_slots.defined() && rep_reply_slots.numel())
+            ? rep_reply_slots.data_ptr<int>() : nullptr;
+    run_round_mlp_comp(false, L, r, d_pids, r_pids, rep_rr, 1);
+}
+
 void tick_pens(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
                torch::Tensor slot_ages, torch::Tensor nodes, torch::Tensor ptr,
                torch::Tensor cslots, torch::Tensor cowners,
@@ -3016,6 +3480,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           "fused item-block merge + per-rating MF SGD tick (K9/K10)");
     m.def("run_round_mlp", &run_round_mlp,
           "whole-round executor, MLP family",
+          py::call_guard<py::gil_scoped_release>());
+    m.def("tick_mlp_part", &tick_mlp_part,
+          "fused partition-merge + age-rescaled MLP SGD tick");
+    m.def("tick_mlp_samp", &tick_mlp_samp,
+          "fused sampled-merge + MLP SGD tick");
+    m.def("run_round_mlp_part", &run_round_mlp_part,
+          "whole-round executor, partitioned MLP family",
+          py::call_guard<py::gil_scoped_release>());
+    m.def("run_round_mlp_samp", &run_round_mlp_samp,
+          "whole-round executor, sampled MLP family",
           py::call_guard<py::gil_scoped_release>());
     m.def("run_round_logreg_samp", &run_round_logreg_samp,
           "whole-round executor, sampled logreg family",
