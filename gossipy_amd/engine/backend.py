@@ -1696,6 +1696,67 @@ class HIPBackend(TorchBackend):
             self._part_cache[key] = hit
         return hit
 
+    def _family_call(self, spec, dev):
+        """The one mapping from a spec to extension arguments. Returns
+        ``(name, args, chan)``:
+
+        * the ops are ``tick_<name>`` and, for the families the whole-round
+          executor admits, ``run_round_<name>``;
+        * ``args`` is the family argument tuple both ops take after the data
+          arena (a tick op appends ``update_only``, a round op
+          ``rep_reply_slots``);
+        * ``chan`` names what rides the per-delivery channel: ``"pids"``
+          (partition ids or sample seeds; tick ops take them after
+          ``reply_slots``), ``"dmodes"`` (pass-through coins, the last tick
+          argument) or ``None``.
+
+        Raises ``ValueError`` for a family/variant without HIP kernels."""
+        fam = spec.family
+        mode = _MODE_ID[spec.mode]
+        if fam in ("logreg", "mlp"):
+            sgd = (
+                spec.lr,
+                spec.weight_decay,
+                max(1, spec.local_epochs),
+                spec.batch_size,
+                mode,
+            )
+            if fam == "logreg":
+                shape = (spec.d_in, spec.n_classes)
+            else:
+                shape = (self._mlp_layout(spec, dev), len(spec.layer_offsets()))
+        if getattr(spec, "n_parts", 0) > 0:
+            if fam not in ("logreg", "mlp"):
+                raise ValueError(
+                    f"partitioned gossip has no HIP path for family {fam!r}"
+                )
+            tables = (*self._part_dev(spec, dev), spec.n_parts)
+            if fam == "mlp":
+                return "mlp_part", (*shape, *tables, *sgd), "pids"
+            return "logreg_part", (*tables, *shape, *sgd), "pids"
+        if fam == "mf":
+            return "mf", (spec.k, spec.n_items, spec.reg, spec.lr), None
+        if fam == "kmeans":
+            return "kmeans", (spec.k, spec.dim, spec.alpha, mode), None
+        if getattr(spec, "sample_size", 0) > 0:
+            if fam not in ("logreg", "mlp"):
+                raise ValueError(
+                    f"sampled gossip has no HIP path for family {fam!r}"
+                )
+            if fam == "mlp":
+                return "mlp_samp", (*shape, spec.samp_count(), *sgd), "pids"
+            return "logreg_samp", (spec.samp_count(), *shape, *sgd), "pids"
+        if fam in ("logreg", "mlp"):
+            return fam, (*shape, *sgd), "dmodes"
+        if fam in ("pegasos", "adaline"):
+            peg = fam == "pegasos"
+            return (
+                "linear",
+                (spec.d_in, spec.lam if peg else spec.lr, int(peg), mode),
+                "dmodes",
+            )
+        raise ValueError(fam)
+
     def _dispatch(
         self, state, pool, data, spec, nodes, recv_ptr, del_slots, reply_slots,
         del_pids, update_only
@@ -1711,93 +1772,14 @@ class HIPBackend(TorchBackend):
             recv_ptr = torch.zeros(len(nodes) + 1, dtype=torch.int32, device=dev)
         else:
             slots, slot_ages = pool.slots, pool.slot_ages
-        mode = _MODE_ID[spec.mode]
-        if getattr(spec, "n_parts", 0) > 0 and spec.family == "mlp":
-            perm, ptr, apart = self._part_dev(spec, dev)
-            self.ext.tick_mlp_part(
-                state.params,
-                state.ages,
-                slots,
-                slot_ages,
-                nodes,
-                recv_ptr,
-                del_slots,
-                reply_slots,
-                del_pids,
-                data.x,
-                data.y,
-                data.counts,
-                self._mlp_layout(spec, dev),
-                len(spec.layer_offsets()),
-                perm,
-                ptr,
-                apart,
-                spec.n_parts,
-                spec.lr,
-                spec.weight_decay,
-                max(1, spec.local_epochs),
-                spec.batch_size,
-                mode,
-                bool(update_only),
-            )
-        elif getattr(spec, "n_parts", 0) > 0:
-            if spec.family != "logreg":
-                raise ValueError(
-                    f"partitioned gossip has no HIP path for family"
-                    f" {spec.family!r}"
-                )
-            perm, ptr, apart = self._part_dev(spec, dev)
-            self.ext.tick_logreg_part(
-                state.params,
-                state.ages,
-                slots,
-                slot_ages,
-                nodes,
-                recv_ptr,
-                del_slots,
-                reply_slots,
-                del_pids,
-                data.x,
-                data.y,
-                data.counts,
-                perm,
-                ptr,
-                apart,
-                spec.n_parts,
-                spec.d_in,
-                spec.n_classes,
-                spec.lr,
-                spec.weight_decay,
-                max(1, spec.local_epochs),
-                spec.batch_size,
-                mode,
-                bool(update_only),
-            )
-        elif spec.family == "mf":
+        name, args, chan = self._family_call(spec, dev)
+        if name == "mf":
             if not update_only and spec.mode != CreateModelMode.MERGE_UPDATE:
                 raise ValueError(
                     "MF engine supports MERGE_UPDATE only (item-block"
                     " transport cannot adopt the sender's user factors)"
                 )
-            self.ext.tick_mf(
-                state.params,
-                state.ages,
-                slots,
-                slot_ages,
-                nodes,
-                recv_ptr,
-                del_slots,
-                reply_slots,
-                data.x,
-                data.y,
-                data.counts,
-                spec.k,
-                spec.n_items,
-                spec.reg,
-                spec.lr,
-                bool(update_only),
-            )
-        elif spec.family == "kmeans":
+        elif name == "kmeans":
             if not update_only and spec.matching != "naive":
                 raise ValueError(
                     "kmeans HIP path implements naive matching (the"
@@ -1805,156 +1787,28 @@ class HIPBackend(TorchBackend):
                     " gossipy/model/handler.py:629-630); use the torch"
                     " backend for the bug-fixed hungarian merge"
                 )
-            self.ext.tick_kmeans(
-                state.params,
-                state.ages,
-                slots,
-                slot_ages,
-                nodes,
-                recv_ptr,
-                del_slots,
-                reply_slots,
-                data.x,
-                data.counts,
-                spec.k,
-                spec.dim,
-                spec.alpha,
-                mode,
-                bool(update_only),
-            )
-        elif getattr(spec, "sample_size", 0) > 0 and spec.family == "mlp":
-            self.ext.tick_mlp_samp(
-                state.params,
-                state.ages,
-                slots,
-                slot_ages,
-                nodes,
-                recv_ptr,
-                del_slots,
-                reply_slots,
-                del_pids,
-                data.x,
-                data.y,
-                data.counts,
-                self._mlp_layout(spec, dev),
-                len(spec.layer_offsets()),
-                spec.samp_count(),
-                spec.lr,
-                spec.weight_decay,
-                max(1, spec.local_epochs),
-                spec.batch_size,
-                mode,
-                bool(update_only),
-            )
-        elif getattr(spec, "sample_size", 0) > 0:
-            if spec.family != "logreg":
-                raise ValueError(
-                    f"sampled gossip has no HIP path for family"
-                    f" {spec.family!r}"
-                )
-            self.ext.tick_logreg_samp(
-                state.params,
-                state.ages,
-                slots,
-                slot_ages,
-                nodes,
-                recv_ptr,
-                del_slots,
-                reply_slots,
-                del_pids,
-                data.x,
-                data.y,
-                data.counts,
-                spec.samp_count(),
-                spec.d_in,
-                spec.n_classes,
-                spec.lr,
-                spec.weight_decay,
-                max(1, spec.local_epochs),
-                spec.batch_size,
-                mode,
-                bool(update_only),
-            )
-        else:
+        events = (nodes, recv_ptr, del_slots, reply_slots)
+        tail = (bool(update_only),)
+        if chan == "pids":
+            events += (del_pids,)
+        elif chan == "dmodes":
             # plain families: pass-through resolves deliveries to PASS via
             # the per-delivery dmodes channel (del_pids carries the coin)
-            dmodes = (
+            tail += (
                 del_pids
                 if getattr(spec, "pass_through", False) and del_pids.numel()
-                else torch.zeros(0, dtype=torch.int32, device=dev)
+                else torch.zeros(0, dtype=torch.int32, device=dev),
             )
-            if spec.family == "logreg":
-                self.ext.tick_logreg(
-                    state.params,
-                    state.ages,
-                    slots,
-                    slot_ages,
-                    nodes,
-                    recv_ptr,
-                    del_slots,
-                    reply_slots,
-                    data.x,
-                    data.y,
-                    data.counts,
-                    spec.d_in,
-                    spec.n_classes,
-                    spec.lr,
-                    spec.weight_decay,
-                    max(1, spec.local_epochs),
-                    spec.batch_size,
-                    mode,
-                    bool(update_only),
-                    dmodes,
-                )
-            elif spec.family in ("pegasos", "adaline"):
-                self.ext.tick_linear(
-                    state.params,
-                    state.ages,
-                    slots,
-                    slot_ages,
-                    nodes,
-                    recv_ptr,
-                    del_slots,
-                    reply_slots,
-                    data.x,
-                    data.y,
-                    data.counts,
-                    spec.d_in,
-                    spec.lam if spec.family == "pegasos" else spec.lr,
-                    1 if spec.family == "pegasos" else 0,
-                    mode,
-                    bool(update_only),
-                    dmodes,
-                )
-            elif spec.family == "mlp":
-                self.ext.tick_mlp(
-                    state.params,
-                    state.ages,
-                    slots,
-                    slot_ages,
-                    nodes,
-                    recv_ptr,
-                    del_slots,
-                    reply_slots,
-                    data.x,
-                    data.y,
-                    data.counts,
-                    torch.tensor(
-                        [x for t in spec.layer_offsets() for x in t],
-                        dtype=torch.int32,
-                        device=dev,
-                    ),
-                    len(spec.layer_offsets()),
-                    spec.lr,
-                    spec.weight_decay,
-                    max(1, spec.local_epochs),
-                    spec.batch_size,
-                    mode,
-                    bool(update_only),
-                    dmodes,
-                )
-            else:
-                raise ValueError(spec.family)
+        # k-means is unsupervised: its tick takes no labels
+        arena = (
+            (data.x, data.counts)
+            if name == "kmeans"
+            else (data.x, data.y, data.counts)
+        )
+        getattr(self.ext, "tick_" + name)(
+            state.params, state.ages, slots, slot_ages, *events, *arena,
+            *args, *tail,
+        )
 
 
 def make_backend(device: torch.device):

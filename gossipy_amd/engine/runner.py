@@ -1230,37 +1230,40 @@ class BatchedGossipSimulator(SimulationEventSender):
             for n in ("snap_tptr", "recv_tptr", "pull_tptr", "rep_tptr")
         }
         ext = self.backend.ext
-        common = (
-            self.state.params,
-            self.state.ages,
-            self.pool.slots,
-            self.pool.slot_ages,
-            views["snap_nodes"],
-            views["snap_slots"],
-            tp["snap_tptr"],
-            views["recv_nodes"],
-            views["recv_nptr"],
-            tp["recv_tptr"],
-            views["del_slots"],
-            views["reply_slots"],
-            views["pull_nodes"],
-            views["pull_slots"],
-            tp["pull_tptr"],
-            views["rep_nodes"],
-            views["rep_nptr"],
-            tp["rep_tptr"],
-            views["rep_slots"],
-            self.data.x,
-            self.data.y,
-            self.data.counts,
-        )
-        from .backend import _MODE_ID
+
+        def leading(tptr):
+            # the block every run_round_* op starts with
+            return (
+                self.state.params,
+                self.state.ages,
+                self.pool.slots,
+                self.pool.slot_ages,
+                views["snap_nodes"],
+                views["snap_slots"],
+                tptr["snap_tptr"],
+                views["recv_nodes"],
+                views["recv_nptr"],
+                tptr["recv_tptr"],
+                views["del_slots"],
+                views["reply_slots"],
+                views["del_pids"],
+                views["pull_nodes"],
+                views["pull_slots"],
+                tptr["pull_tptr"],
+                views["rep_nodes"],
+                views["rep_nptr"],
+                tptr["rep_tptr"],
+                views["rep_slots"],
+                views["rep_pids"],
+                self.data.x,
+                self.data.y,
+                self.data.counts,
+            )
 
         spec = self.spec
+        name, args, _ = self.backend._family_call(spec, dev)
         if (
-            spec.family == "logreg"
-            and getattr(spec, "n_parts", 0) == 0
-            and getattr(spec, "sample_size", 0) == 0
+            name == "logreg"
             and not getattr(spec, "pass_through", False)
             and getattr(self, "_coop_enabled", True)
             and os.environ.get("GOSSIPY_COOP") == "1"
@@ -1270,49 +1273,14 @@ class BatchedGossipSimulator(SimulationEventSender):
             # ms/round at the flagship config: ~200 grid.sync barriers cost
             # more than ~200 stream launch gaps), so opt-in only
             # (GOSSIPY_COOP=1); kept as the measured alternative
-            per_tick = []
-            for name in ("snap_tptr", "recv_tptr", "pull_tptr", "rep_tptr"):
-                dif = np.diff(f[name])
-                if len(dif):
-                    per_tick.append(int(dif.max()))
+            per_tick = [
+                int(np.diff(f[n]).max()) for n in tp if len(f[n]) > 1
+            ]
             max_batch = max(per_tick) if per_tick else 1
-            tpd = {
-                n: torch.from_numpy(
-                    np.ascontiguousarray(f[n], dtype=np.int32)
-                ).to(dev)
-                for n in ("snap_tptr", "recv_tptr", "pull_tptr", "rep_tptr")
-            }
             try:
                 ext.run_round_coop_logreg(
-                    self.state.params,
-                    self.state.ages,
-                    self.pool.slots,
-                    self.pool.slot_ages,
-                    views["snap_nodes"],
-                    views["snap_slots"],
-                    tpd["snap_tptr"],
-                    views["recv_nodes"],
-                    views["recv_nptr"],
-                    tpd["recv_tptr"],
-                    views["del_slots"],
-                    views["reply_slots"],
-                    views["pull_nodes"],
-                    views["pull_slots"],
-                    tpd["pull_tptr"],
-                    views["rep_nodes"],
-                    views["rep_nptr"],
-                    tpd["rep_tptr"],
-                    views["rep_slots"],
-                    self.data.x,
-                    self.data.y,
-                    self.data.counts,
-                    spec.d_in,
-                    spec.n_classes,
-                    spec.lr,
-                    spec.weight_decay,
-                    max(1, spec.local_epochs),
-                    spec.batch_size,
-                    _MODE_ID[spec.mode],
+                    *leading({n: t.to(dev) for n, t in tp.items()}),
+                    *args,
                     max_batch,
                 )
                 return
@@ -1321,123 +1289,9 @@ class BatchedGossipSimulator(SimulationEventSender):
                             "falling back to the stream executor", e)
                 self._coop_enabled = False
 
-        # executor by (family, n_parts, sample_size)
-        n_parts = getattr(spec, "n_parts", 0)
-        sample_size = getattr(spec, "sample_size", 0)
-        if spec.family == "mlp" and (n_parts > 0 or sample_size > 0):
-            # same del_pids/rep_pids positions as the logreg variants
-            c = list(common)
-            c.insert(12, views["del_pids"])   # after reply_slots
-            c.insert(20, views["rep_pids"])   # after rep_slots
-            c += [
-                self.backend._mlp_layout(spec, dev),
-                len(spec.layer_offsets()),
-            ]
-            tail = (
-                spec.lr,
-                spec.weight_decay,
-                max(1, spec.local_epochs),
-                spec.batch_size,
-                _MODE_ID[spec.mode],
-                views["rep_reply_slots"],
-            )
-            if n_parts > 0:
-                perm, pptr, apart = self.backend._part_dev(spec, dev)
-                ext.run_round_mlp_part(
-                    *c, perm, pptr, apart, spec.n_parts, *tail
-                )
-            else:
-                ext.run_round_mlp_samp(*c, spec.samp_count(), *tail)
-        elif sample_size > 0:
-            if spec.family != "logreg":
-                raise ValueError(
-                    f"sampled gossip has no round executor for family"
-                    f" {spec.family!r}"
-                )
-            c = list(common)
-            c.insert(12, views["del_pids"])   # sample seeds ride the pid slot
-            c.insert(20, views["rep_pids"])
-            ext.run_round_logreg_samp(
-                *c,
-                spec.samp_count(),
-                spec.d_in,
-                spec.n_classes,
-                spec.lr,
-                spec.weight_decay,
-                max(1, spec.local_epochs),
-                spec.batch_size,
-                _MODE_ID[spec.mode],
-                views["rep_reply_slots"],
-            )
-        elif spec.family == "mf":
-            ext.run_round_mf(
-                *common,
-                spec.k,
-                spec.n_items,
-                spec.reg,
-                spec.lr,
-                views["rep_reply_slots"],
-            )
-        elif getattr(spec, "n_parts", 0) > 0:
-            perm, pptr, apart = self.backend._part_dev(spec, dev)
-            # run_round_logreg_part takes del_pids after reply_slots and
-            # rep_pids after rep_slots
-            c = list(common)
-            c.insert(12, views["del_pids"])   # after reply_slots
-            c.insert(20, views["rep_pids"])   # after rep_slots
-            ext.run_round_logreg_part(
-                *c,
-                perm,
-                pptr,
-                apart,
-                spec.n_parts,
-                spec.d_in,
-                spec.n_classes,
-                spec.lr,
-                spec.weight_decay,
-                max(1, spec.local_epochs),
-                spec.batch_size,
-                _MODE_ID[spec.mode],
-                views["rep_reply_slots"],
-            )
-        elif spec.family == "logreg":
-            ext.run_round_logreg(
-                *common,
-                spec.d_in,
-                spec.n_classes,
-                spec.lr,
-                spec.weight_decay,
-                max(1, spec.local_epochs),
-                spec.batch_size,
-                _MODE_ID[spec.mode],
-                views["rep_reply_slots"],
-            )
-        elif spec.family == "mlp":
-            layout = torch.tensor(
-                [x for tup in spec.layer_offsets() for x in tup],
-                dtype=torch.int32,
-                device=dev,
-            )
-            ext.run_round_mlp(
-                *common,
-                layout,
-                len(spec.layer_offsets()),
-                spec.lr,
-                spec.weight_decay,
-                max(1, spec.local_epochs),
-                spec.batch_size,
-                _MODE_ID[spec.mode],
-                views["rep_reply_slots"],
-            )
-        else:
-            ext.run_round_linear(
-                *common,
-                spec.d_in,
-                spec.lam if spec.family == "pegasos" else spec.lr,
-                1 if spec.family == "pegasos" else 0,
-                _MODE_ID[spec.mode],
-                views["rep_reply_slots"],
-            )
+        getattr(ext, "run_round_" + name)(
+            *leading(tp), *args, views["rep_reply_slots"]
+        )
 
     def start(self, n_rounds: int = 100) -> None:
         """Run ``n_rounds`` rounds."""

@@ -2131,6 +2131,43 @@ static hipStream_t current_stream()
     return at::hip::getCurrentHIPStream().stream();
 }
 
+// device pointer of an optional int array: null when empty or undefined
+static const int* iptr(const torch::Tensor& t)
+{
+    return (t.defined() && t.numel()) ? t.data_ptr<int>() : nullptr;
+}
+
+// Launch of a kernel held as a pointer (a plan picks it at run time):
+// hipLaunchKernel is the call a `<<<>>>` launch makes underneath.
+template <typename Args>
+static void launch_kernel(void (*kernel)(Args), int grid, int block,
+                          size_t smem, hipStream_t s, Args& a)
+{
+    void* kargs[] = {&a};
+    hipError_t err = hipLaunchKernel((const void*)kernel, dim3(grid),
+                                     dim3(block), kargs, smem, s);
+    TORCH_CHECK(err == hipSuccess, "kernel launch failed: ",
+                hipGetErrorString(err));
+}
+
+// What a snapshot of one row copies: W floats from column src_off of a
+// Dp-wide params row, and age_w ages.
+struct SnapGeom {
+    int W, Dp, src_off, age_w;
+};
+
+static void launch_snap(const float* params, const int* ages, float* slots,
+                        int* slot_ages, const int* nodes, const int* slot_ids,
+                        int n, const SnapGeom& g, hipStream_t s)
+{
+    long total = (long)n * g.W;
+    int block = 256;
+    int grid = (int)std::min<long>((total + block - 1) / block, 2048);
+    hipLaunchKernelGGL(snapshot_kernel, dim3(grid), dim3(block), 0, s,
+                       params, ages, slots, slot_ages, nodes, slot_ids, n,
+                       g.W, g.Dp, g.src_off, g.age_w);
+}
+
 void snapshot(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
               torch::Tensor slot_ages, torch::Tensor nodes, torch::Tensor slot_ids,
               int64_t age_width, int64_t src_off)
@@ -2138,16 +2175,12 @@ void snapshot(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
     CHECK_DEV(params); CHECK_DEV(slots); CHECK_DEV(nodes); CHECK_DEV(slot_ids);
     int n = nodes.size(0);
     if (n == 0) return;
-    int W = slots.size(1);
-    int Dp = params.size(1);
-    long total = (long)n * W;
-    int block = 256;
-    int grid = (int)std::min<long>((total + block - 1) / block, 2048);
-    hipLaunchKernelGGL(snapshot_kernel, dim3(grid), dim3(block), 0, current_stream(),
-        params.data_ptr<float>(), ages.data_ptr<int>(),
-        slots.data_ptr<float>(), slot_ages.data_ptr<int>(),
-        nodes.data_ptr<int>(), slot_ids.data_ptr<int>(), n, W, Dp,
-        (int)src_off, (int)age_width);
+    SnapGeom g{(int)slots.size(1), (int)params.size(1), (int)src_off,
+               (int)age_width};
+    launch_snap(params.data_ptr<float>(), ages.data_ptr<int>(),
+                slots.data_ptr<float>(), slot_ages.data_ptr<int>(),
+                nodes.data_ptr<int>(), slot_ids.data_ptr<int>(), n, g,
+                current_stream());
 }
 
 void wmerge(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
@@ -2167,224 +2200,216 @@ void wmerge(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
         selfw.data_ptr<float>(), D);
 }
 
-void tick_logreg_part(
-    torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
-    torch::Tensor slot_ages, torch::Tensor nodes, torch::Tensor recv_ptr,
-    torch::Tensor del_slots, torch::Tensor reply_slots, torch::Tensor del_pids,
-    torch::Tensor X, torch::Tensor Y, torch::Tensor counts,
-    torch::Tensor perm, torch::Tensor pptr, torch::Tensor apart,
-    int64_t n_parts, int64_t d, int64_t k, double lr, double wd,
-    int64_t epochs, int64_t bs, int64_t mode, bool update_only)
+// ---------------------------------------------------------------------------
+// launch plans: everything about a family's launch that depends on the spec
+// alone, built by ONE function per family that both its tick_X and its
+// run_round_X entry point call. A plan holds the args struct with every
+// per-spec field filled and every check done, the kernel, its dynamic LDS
+// and block size, and the snapshot geometry of the family's rows. The
+// per-call event pointers (nodes, ptr, dslots, rslots, update_only and the
+// family's per-delivery channel: dmodes / dpids / dseeds) are left to
+// launch_tick and stream_round.
+// ---------------------------------------------------------------------------
+
+template <typename Args>
+struct Plan {
+    Args a{};
+    void (*kernel)(Args) = nullptr;
+    size_t smem = 0;
+    int threads = 0;
+    SnapGeom snap{};
+};
+
+// the per-delivery channel of a family: a `const int*` member of its args
+template <typename Args>
+struct channel {
+    using type = const int* Args::*;
+};
+
+// the arena, pool and data tensors every family's entry points take
+struct StateTensors {
+    torch::Tensor params, ages, slots, slot_ages, X, Y, counts;
+};
+
+template <typename A>
+static void fill_state_x(A& a, const StateTensors& st)
 {
-    CHECK_DEV(params); CHECK_DEV(slots); CHECK_DEV(X); CHECK_DEV(Y);
+    const torch::Tensor &params = st.params, &slots = st.slots, &X = st.X;
+    CHECK_DEV(params); CHECK_DEV(slots); CHECK_DEV(X);
+    a.params = params.data_ptr<float>(); a.ages = st.ages.data_ptr<int>();
+    a.slots = slots.data_ptr<float>(); a.slot_ages = st.slot_ages.data_ptr<int>();
+    a.X = X.data_ptr<float>(); a.counts = st.counts.data_ptr<int>();
+    a.Smax = X.size(1);
+}
+
+template <typename A>
+static void fill_state(A& a, const StateTensors& st)
+{
+    fill_state_x(a, st);
+    const torch::Tensor& Y = st.Y;
+    CHECK_DEV(Y);
+    a.Y = Y.data_ptr<float>();
+}
+
+template <typename A>
+static void fill_sgd(A& a, double lr, double wd, int64_t epochs, int64_t bs,
+                     int64_t mode)
+{
+    a.lr = lr; a.wd = wd; a.epochs = epochs; a.bs = bs; a.mode = mode;
+}
+
+// rows of the largest minibatch (bs == 0: the whole shard)
+static int batch_rows(int64_t bs, int Smax)
+{
+    return (bs == 0) ? Smax : std::min<int>(bs, Smax);
+}
+
+// the event fields live in the args struct itself, except that the
+// compressed MLP wraps a plain MlpArgs
+template <typename A> static A& events(A& a) { return a; }
+static MlpArgs& events(MlpCompArgs& c) { return c.m; }
+
+static Plan<LogregArgs> logreg_plan(
+    const StateTensors& st, int64_t d, int64_t k, double lr, double wd,
+    int64_t epochs, int64_t bs, int64_t mode)
+{
+    Plan<LogregArgs> L;
+    LogregArgs& a = L.a;
+    fill_state(a, st);
+    TORCH_CHECK(k <= KMAX, "n_classes > ", KMAX, " unsupported");
+    a.d = d; a.k = k; a.D = st.params.size(1);
+    fill_sgd(a, lr, wd, epochs, bs, mode);
+    int bsmax = batch_rows(bs, a.Smax);
+    L.smem = sizeof(float) * (2 * a.D + (size_t)bsmax * a.d + (size_t)bsmax * a.k);
+    TORCH_CHECK(L.smem <= 160 * 1024, "logreg LDS budget exceeded: ", L.smem);
+    L.kernel = tick_logreg_kernel;
+    L.threads = 128;
+    L.snap = {a.D, a.D, 0, 1};
+    return L;
+}
+
+static Plan<LinearArgs> linear_plan(
+    const StateTensors& st, int64_t d, double lrlam, int64_t is_pegasos,
+    int64_t mode)
+{
+    Plan<LinearArgs> L;
+    LinearArgs& a = L.a;
+    fill_state(a, st);
+    TORCH_CHECK(d <= LIN_MAX_REGS * WAVE, "d > ", LIN_MAX_REGS * WAVE, " unsupported");
+    a.d = d;
+    a.lrlam = lrlam; a.is_pegasos = is_pegasos; a.mode = mode;
+    L.kernel = tick_linear_kernel;
+    L.threads = WAVE;
+    L.snap = {a.d, a.d, 0, 1};
+    return L;
+}
+
+static Plan<LogregPartArgs> logreg_part_plan(
+    const StateTensors& st, torch::Tensor perm, torch::Tensor pptr,
+    torch::Tensor apart, int64_t n_parts, int64_t d, int64_t k, double lr,
+    double wd, int64_t epochs, int64_t bs, int64_t mode)
+{
+    Plan<LogregPartArgs> L;
+    LogregPartArgs& a = L.a;
+    fill_state(a, st);
     CHECK_DEV(perm); CHECK_DEV(pptr); CHECK_DEV(apart);
     TORCH_CHECK(k <= KMAX, "n_classes > ", KMAX, " unsupported");
     TORCH_CHECK(mode != MODE_PASS, "Mode PASS not allowed for partitioned models.");
-    int n = nodes.size(0);
-    if (n == 0) return;
-    LogregPartArgs a;
-    a.params = params.data_ptr<float>(); a.ages = ages.data_ptr<int>();
-    a.slots = slots.data_ptr<float>(); a.slot_ages = slot_ages.data_ptr<int>();
-    a.nodes = nodes.data_ptr<int>(); a.ptr = recv_ptr.data_ptr<int>();
-    a.dslots = del_slots.numel() ? del_slots.data_ptr<int>() : nullptr;
-    a.rslots = reply_slots.numel() ? reply_slots.data_ptr<int>() : nullptr;
-    a.dpids = del_pids.numel() ? del_pids.data_ptr<int>() : nullptr;
-    a.X = X.data_ptr<float>(); a.Y = Y.data_ptr<float>();
-    a.counts = counts.data_ptr<int>();
     a.perm = perm.data_ptr<int>(); a.pptr = pptr.data_ptr<int>();
     a.apart = apart.data_ptr<int>();
-    a.P = n_parts; a.d = d; a.k = k; a.Smax = X.size(1); a.D = params.size(1);
-    a.lr = lr; a.wd = wd; a.epochs = epochs; a.bs = bs; a.mode = mode;
-    a.update_only = update_only;
-    int bsmax = (bs == 0) ? a.Smax : std::min<int>(bs, a.Smax);
+    a.P = n_parts; a.d = d; a.k = k; a.D = st.params.size(1);
+    fill_sgd(a, lr, wd, epochs, bs, mode);
+    int bsmax = batch_rows(bs, a.Smax);
     // whole-shard staging when it fits a 64 KB block budget (keeps >=2
-    // blocks/CU); otherwise per-step slices as before
+    // blocks/CU); otherwise per-step slices
     size_t full = sizeof(float) * (2 * a.D + (size_t)a.Smax * a.d +
                                    (size_t)bsmax * a.k) +
                   sizeof(int) * 2 * a.P;
     a.stage_full = (full <= 64 * 1024) ? 1 : 0;
-    size_t smem = a.stage_full
+    L.smem = a.stage_full
         ? full
         : sizeof(float) * (2 * a.D + (size_t)bsmax * a.d +
                            (size_t)bsmax * a.k) +
               sizeof(int) * 2 * a.P;
-    TORCH_CHECK(smem <= 160 * 1024, "partitioned logreg LDS budget exceeded: ", smem);
-    hipLaunchKernelGGL(tick_logreg_part_kernel, dim3(n), dim3(128), smem,
-                       current_stream(), a);
+    TORCH_CHECK(L.smem <= 160 * 1024, "partitioned logreg LDS budget exceeded: ", L.smem);
+    L.kernel = tick_logreg_part_kernel;
+    L.threads = 128;
+    L.snap = {a.D, a.D, 0, a.P};
+    return L;
 }
 
-void tick_logreg(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
-                 torch::Tensor slot_ages, torch::Tensor nodes, torch::Tensor recv_ptr,
-                 torch::Tensor del_slots, torch::Tensor reply_slots,
-                 torch::Tensor X, torch::Tensor Y, torch::Tensor counts,
-                 int64_t d, int64_t k, double lr, double wd, int64_t epochs,
-                 int64_t bs, int64_t mode, bool update_only,
-                 torch::Tensor dmodes)
+static Plan<LogregSampArgs> logreg_samp_plan(
+    const StateTensors& st, int64_t samp_c, int64_t d, int64_t k, double lr,
+    double wd, int64_t epochs, int64_t bs, int64_t mode)
 {
-    CHECK_DEV(params); CHECK_DEV(slots); CHECK_DEV(X); CHECK_DEV(Y);
+    Plan<LogregSampArgs> L;
+    LogregSampArgs& a = L.a;
+    fill_state(a, st);
     TORCH_CHECK(k <= KMAX, "n_classes > ", KMAX, " unsupported");
-    int n = nodes.size(0);
-    if (n == 0) return;
-    LogregArgs a;
-    a.params = params.data_ptr<float>(); a.ages = ages.data_ptr<int>();
-    a.slots = slots.data_ptr<float>(); a.slot_ages = slot_ages.data_ptr<int>();
-    a.nodes = nodes.data_ptr<int>(); a.ptr = recv_ptr.data_ptr<int>();
-    a.dslots = del_slots.numel() ? del_slots.data_ptr<int>() : nullptr;
-    a.rslots = reply_slots.numel() ? reply_slots.data_ptr<int>() : nullptr;
-    a.X = X.data_ptr<float>(); a.Y = Y.data_ptr<float>();
-    a.counts = counts.data_ptr<int>();
-    a.dmodes = dmodes.numel() ? dmodes.data_ptr<int>() : nullptr;
-    a.d = d; a.k = k; a.Smax = X.size(1); a.D = params.size(1);
-    a.lr = lr; a.wd = wd; a.epochs = epochs; a.bs = bs; a.mode = mode;
-    a.update_only = update_only;
-    int bsmax = (bs == 0) ? a.Smax : std::min<int>(bs, a.Smax);
-    size_t smem = sizeof(float) * (2 * a.D + (size_t)bsmax * a.d + (size_t)bsmax * a.k);
-    TORCH_CHECK(smem <= 160 * 1024, "logreg LDS budget exceeded: ", smem);
-    hipLaunchKernelGGL(tick_logreg_kernel, dim3(n), dim3(128), smem,
-                       current_stream(), a);
+    TORCH_CHECK(mode != MODE_PASS, "Mode PASS not allowed for sampled models.");
+    a.samp_c = samp_c; a.d = d; a.k = k; a.D = st.params.size(1);
+    fill_sgd(a, lr, wd, epochs, bs, mode);
+    int bsmax = batch_rows(bs, a.Smax);
+    L.smem = sizeof(float) * (3 * a.D + (size_t)bsmax * a.d +
+                              (size_t)bsmax * a.k);
+    TORCH_CHECK(L.smem <= 160 * 1024, "sampled logreg LDS budget exceeded: ", L.smem);
+    L.kernel = tick_logreg_samp_kernel;
+    L.threads = 128;
+    L.snap = {a.D, a.D, 0, 1};
+    return L;
 }
 
-void tick_linear(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
-                 torch::Tensor slot_ages, torch::Tensor nodes, torch::Tensor recv_ptr,
-                 torch::Tensor del_slots, torch::Tensor reply_slots,
-                 torch::Tensor X, torch::Tensor Y, torch::Tensor counts,
-                 int64_t d, double lrlam, int64_t is_pegasos, int64_t mode,
-                 bool update_only, torch::Tensor dmodes)
+static Plan<MFArgs> mf_plan(const StateTensors& st, int64_t k, int64_t n_items,
+                            double reg, double lr)
 {
-    CHECK_DEV(params); CHECK_DEV(slots); CHECK_DEV(X); CHECK_DEV(Y);
-    TORCH_CHECK(d <= LIN_MAX_REGS * WAVE, "d > ", LIN_MAX_REGS * WAVE, " unsupported");
-    int n = nodes.size(0);
-    if (n == 0) return;
-    LinearArgs a;
-    a.params = params.data_ptr<float>(); a.ages = ages.data_ptr<int>();
-    a.slots = slots.data_ptr<float>(); a.slot_ages = slot_ages.data_ptr<int>();
-    a.nodes = nodes.data_ptr<int>(); a.ptr = recv_ptr.data_ptr<int>();
-    a.dslots = del_slots.numel() ? del_slots.data_ptr<int>() : nullptr;
-    a.rslots = reply_slots.numel() ? reply_slots.data_ptr<int>() : nullptr;
-    a.X = X.data_ptr<float>(); a.Y = Y.data_ptr<float>();
-    a.counts = counts.data_ptr<int>();
-    a.dmodes = dmodes.numel() ? dmodes.data_ptr<int>() : nullptr;
-    a.d = d; a.Smax = X.size(1);
-    a.lrlam = lrlam; a.is_pegasos = is_pegasos; a.mode = mode;
-    a.update_only = update_only;
-    hipLaunchKernelGGL(tick_linear_kernel, dim3(n), dim3(WAVE), 0,
-                       current_stream(), a);
+    Plan<MFArgs> L;
+    MFArgs& a = L.a;
+    fill_state(a, st);
+    TORCH_CHECK(k <= WAVE, "MF latent dim > ", WAVE, " unsupported");
+    a.k = k; a.n_items = n_items; a.D = st.params.size(1);
+    a.item_off = k + 1; a.Wslot = n_items * (k + 1);
+    a.reg = reg; a.lr = lr;
+    L.kernel = tick_mf_kernel;
+    L.threads = 256;
+    // MF snapshots carry only the item block
+    L.snap = {a.Wslot, a.D, a.item_off, 1};
+    return L;
 }
 
-void tick_mlp(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
-              torch::Tensor slot_ages, torch::Tensor nodes, torch::Tensor recv_ptr,
-              torch::Tensor del_slots, torch::Tensor reply_slots,
-              torch::Tensor X, torch::Tensor Y, torch::Tensor counts,
-              torch::Tensor layout, int64_t n_layers, double lr, double wd,
-              int64_t epochs, int64_t bs, int64_t mode, bool update_only,
-              torch::Tensor dmodes)
+static Plan<KMeansArgs> kmeans_plan(const StateTensors& st, int64_t k,
+                                    int64_t dim, double alpha, int64_t mode)
 {
-    CHECK_DEV(params); CHECK_DEV(slots); CHECK_DEV(X); CHECK_DEV(Y);
-    CHECK_DEV(layout);
-    int n = nodes.size(0);
-    if (n == 0) return;
-    MlpArgs a;
-    a.params = params.data_ptr<float>(); a.ages = ages.data_ptr<int>();
-    a.slots = slots.data_ptr<float>(); a.slot_ages = slot_ages.data_ptr<int>();
-    a.nodes = nodes.data_ptr<int>(); a.ptr = recv_ptr.data_ptr<int>();
-    a.dslots = del_slots.numel() ? del_slots.data_ptr<int>() : nullptr;
-    a.rslots = reply_slots.numel() ? reply_slots.data_ptr<int>() : nullptr;
-    a.X = X.data_ptr<float>(); a.Y = Y.data_ptr<float>();
-    a.counts = counts.data_ptr<int>();
-    a.layout = layout.data_ptr<int>();
-    a.dmodes = dmodes.numel() ? dmodes.data_ptr<int>() : nullptr;
-    a.n_layers = n_layers; a.Smax = X.size(1); a.D = params.size(1);
-    a.d_in = layout[2].item<int>();
-    a.lr = lr; a.wd = wd; a.epochs = epochs; a.bs = bs; a.mode = mode;
-    a.update_only = update_only;
-    // LDS: 2*D (model + scratch) + activations + 2 grad buffers
-    auto lay = layout.cpu();
-    const int* L = lay.data_ptr<int>();
-    int act_sum = 0, act_max = L[2];
-    for (int l = 0; l < n_layers; ++l) {
-        act_sum += L[4 * l + 3];
-        act_max = std::max(act_max, L[4 * l + 3]);
-        act_max = std::max(act_max, L[4 * l + 2]);
-    }
-    a.act_max = act_max;
-    a.d_in = L[2];
-    int bsmax = (bs == 0) ? a.Smax : std::min<int>(bs, a.Smax);
-    size_t w_slabs = (mode == MODE_UPDATE_MERGE) ? 2 : 1;  // W2 only there
-    size_t smem = sizeof(float) *
-        (w_slabs * (size_t)a.D + (size_t)bsmax * (a.d_in + act_sum) +
-         2 * (size_t)bsmax * act_max);
-    TORCH_CHECK(smem <= 160 * 1024,
-        "mlp LDS budget exceeded (", smem, " B); shrink batch_size/hidden");
-    // block size: 8 waves when any GEMM stage has >= 8 MFMA tiles (halves
-    // the sequential tile passes of the widest stage — e.g. dW [100,57] is
-    // 28 tiles), else the default 4 waves
-    int max_tiles = 0;
-    {
-        int m16 = (bsmax + 15) >> 4;
-        for (int l = 0; l < n_layers; ++l) {
-            int fin16 = (L[4 * l + 2] + 15) >> 4;
-            int fout16 = (L[4 * l + 3] + 15) >> 4;
-            max_tiles = std::max(max_tiles, m16 * fout16);   // forward
-            max_tiles = std::max(max_tiles, m16 * fin16);    // dX
-            max_tiles = std::max(max_tiles, fout16 * fin16); // dW
-        }
-    }
-    int threads = (max_tiles >= 8) ? 512 : 256;
-    hipLaunchKernelGGL(tick_mlp_kernel, dim3(n), dim3(threads), smem,
-                       current_stream(), a);
+    Plan<KMeansArgs> L;
+    KMeansArgs& a = L.a;
+    fill_state_x(a, st);
+    a.k = k; a.dim = dim; a.D = st.params.size(1);
+    a.alpha = alpha; a.mode = mode;
+    L.smem = sizeof(float) * 2 * a.D + sizeof(int) * a.Smax;
+    TORCH_CHECK(L.smem <= 160 * 1024, "kmeans LDS budget exceeded: ", L.smem);
+    L.kernel = tick_kmeans_kernel;
+    L.threads = 128;
+    L.snap = {a.D, a.D, 0, 1};
+    return L;
 }
 
-// Launch geometry of the compressed MLP kernels, shared by the tick and
-// whole-round entry points.
-struct MlpCompLaunch {
-    MlpCompArgs c;
-    size_t smem;
+// What the plain and the compressed MLP plan share: state, layout and SGD
+// fields of the MlpArgs, and the launch geometry the layer shapes imply.
+struct MlpGeom {
+    size_t scratch;  // floats of activations + two grad buffers
     int threads;
 };
 
-// Fills every per-spec field (pointers to the per-call event arrays are
-// left to the caller) and checks the per-mode LDS budget: W, +W2 unless
-// MERGE_UPDATE, +the sampled pre-merge copy unless it fits the act/grad
-// scratch, activations, two grad buffers, 2*P age ints when partitioned.
-static MlpCompLaunch mlp_comp_setup(
-    bool part, torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
-    torch::Tensor slot_ages, torch::Tensor X, torch::Tensor Y,
-    torch::Tensor counts, torch::Tensor layout, int64_t n_layers,
-    int64_t n_parts, int64_t samp_c, double lr, double wd, int64_t epochs,
-    int64_t bs, int64_t mode)
+static MlpGeom mlp_fill(MlpArgs& a, const StateTensors& st,
+                        torch::Tensor layout, int64_t n_layers, double lr,
+                        double wd, int64_t epochs, int64_t bs, int64_t mode)
 {
-    const char* what = part ? "partitioned" : "sampled";
-    CHECK_DEV(params); CHECK_DEV(slots); CHECK_DEV(X); CHECK_DEV(Y);
+    fill_state(a, st);
     CHECK_DEV(layout);
-    TORCH_CHECK(mode != MODE_PASS, "Mode PASS not allowed for ", what,
-                " models.");
     TORCH_CHECK(n_layers >= 1 && layout.numel() == 4 * n_layers,
                 "mlp layout must hold n_layers x (w_off, b_off, in, out)");
-    MlpCompLaunch L;
-    MlpCompArgs& c = L.c;
-    MlpArgs& a = c.m;
-    a.params = params.data_ptr<float>(); a.ages = ages.data_ptr<int>();
-    a.slots = slots.data_ptr<float>(); a.slot_ages = slot_ages.data_ptr<int>();
-    a.nodes = nullptr; a.ptr = nullptr; a.dslots = nullptr; a.rslots = nullptr;
-    a.dmodes = nullptr;
-    a.X = X.data_ptr<float>(); a.Y = Y.data_ptr<float>();
-    a.counts = counts.data_ptr<int>();
     a.layout = layout.data_ptr<int>();
-    a.n_layers = n_layers; a.Smax = X.size(1); a.D = params.size(1);
-    a.lr = lr; a.wd = wd; a.epochs = epochs; a.bs = bs; a.mode = mode;
-    a.update_only = 0;
-    c.dpids = nullptr; c.perm = nullptr; c.pptr = nullptr; c.apart = nullptr;
-    c.P = part ? (int)n_parts : 0;
-    c.samp_c = part ? 0 : (int)samp_c;
-    c.w3_alias = 0;
-    if (part) {
-        TORCH_CHECK(n_parts >= 1, "n_parts must be positive");
-        TORCH_CHECK(ages.numel() == ages.size(0) * n_parts &&
-                    slot_ages.numel() == slot_ages.size(0) * n_parts,
-                    "partitioned mlp: ages and slot_ages must be [*, n_parts]");
-    } else {
-        TORCH_CHECK(samp_c >= 1, "samp_c must be positive");
-    }
+    a.n_layers = n_layers; a.D = st.params.size(1);
+    fill_sgd(a, lr, wd, epochs, bs, mode);
     auto lay = layout.cpu();
     const int* Lh = lay.data_ptr<int>();
     int act_sum = 0, act_max = Lh[2];
@@ -2395,21 +2420,13 @@ static MlpCompLaunch mlp_comp_setup(
     }
     a.act_max = act_max;
     a.d_in = Lh[2];
-    int bsmax = (bs == 0) ? a.Smax : std::min<int>(bs, a.Smax);
-    size_t scratch = (size_t)bsmax * (a.d_in + act_sum) +
-                     2 * (size_t)bsmax * act_max;
-    size_t w_slabs = (mode == MODE_MERGE_UPDATE) ? 1 : 2;
-    if (!part) {
-        c.w3_alias = (scratch >= (size_t)a.D) ? 1 : 0;
-        if (!c.w3_alias) w_slabs += 1;
-    }
-    L.smem = sizeof(float) * (w_slabs * (size_t)a.D + scratch) +
-             sizeof(int) * 2 * (size_t)c.P;
-    TORCH_CHECK(L.smem <= 160 * 1024, what, " mlp LDS budget exceeded (",
-                L.smem, " B > 163840 B); shrink batch_size/hidden, or use"
-                " MERGE_UPDATE (the other modes hold a second model slab)");
-    // block size policy as in tick_mlp: 8 waves when any GEMM stage has
-    // >= 8 MFMA tiles, else 4
+    int bsmax = batch_rows(bs, a.Smax);
+    MlpGeom g;
+    g.scratch = (size_t)bsmax * (a.d_in + act_sum) +
+                2 * (size_t)bsmax * act_max;
+    // block size: 8 waves when any GEMM stage has >= 8 MFMA tiles (halves
+    // the sequential tile passes of the widest stage — e.g. dW [100,57] is
+    // 28 tiles), else the default 4 waves
     int max_tiles = 0;
     int m16 = (bsmax + 15) >> 4;
     for (int l = 0; l < n_layers; ++l) {
@@ -2419,35 +2436,174 @@ static MlpCompLaunch mlp_comp_setup(
         max_tiles = std::max(max_tiles, m16 * fin16);    // dX
         max_tiles = std::max(max_tiles, fout16 * fin16); // dW
     }
-    L.threads = (max_tiles >= 8) ? 512 : 256;
+    g.threads = (max_tiles >= 8) ? 512 : 256;
+    return g;
+}
+
+static Plan<MlpArgs> mlp_plan(
+    const StateTensors& st, torch::Tensor layout, int64_t n_layers, double lr,
+    double wd, int64_t epochs, int64_t bs, int64_t mode)
+{
+    Plan<MlpArgs> L;
+    MlpArgs& a = L.a;
+    MlpGeom g = mlp_fill(a, st, layout, n_layers, lr, wd, epochs, bs, mode);
+    // LDS: model (+ scratch copy W2, UPDATE_MERGE only) + activations +
+    // 2 grad buffers
+    size_t w_slabs = (mode == MODE_UPDATE_MERGE) ? 2 : 1;
+    L.smem = sizeof(float) * (w_slabs * (size_t)a.D + g.scratch);
+    TORCH_CHECK(L.smem <= 160 * 1024,
+        "mlp LDS budget exceeded (", L.smem, " B); shrink batch_size/hidden");
+    L.kernel = tick_mlp_kernel;
+    L.threads = g.threads;
+    L.snap = {a.D, a.D, 0, 1};
     return L;
 }
 
-static void mlp_comp_launch(bool part, const MlpCompLaunch& L, int n,
-                            hipStream_t s)
+// Partitioned (part) or sampled compressed MLP. Checks the per-mode LDS
+// budget: W, +W2 unless MERGE_UPDATE, +the sampled pre-merge copy unless it
+// fits the act/grad scratch, activations, two grad buffers, 2*P age ints
+// when partitioned. The partition tables are read when part only.
+static Plan<MlpCompArgs> mlp_comp_plan(
+    bool part, const StateTensors& st, torch::Tensor layout, int64_t n_layers,
+    torch::Tensor perm, torch::Tensor pptr, torch::Tensor apart,
+    int64_t n_parts, int64_t samp_c, double lr, double wd, int64_t epochs,
+    int64_t bs, int64_t mode)
 {
-    if (part)
-        hipLaunchKernelGGL(tick_mlp_comp_kernel<true>, dim3(n),
-                           dim3(L.threads), L.smem, s, L.c);
-    else
-        hipLaunchKernelGGL(tick_mlp_comp_kernel<false>, dim3(n),
-                           dim3(L.threads), L.smem, s, L.c);
+    const char* what = part ? "partitioned" : "sampled";
+    Plan<MlpCompArgs> L;
+    MlpCompArgs& c = L.a;
+    MlpArgs& a = c.m;
+    TORCH_CHECK(mode != MODE_PASS, "Mode PASS not allowed for ", what,
+                " models.");
+    MlpGeom g = mlp_fill(a, st, layout, n_layers, lr, wd, epochs, bs, mode);
+    c.P = part ? (int)n_parts : 0;
+    c.samp_c = part ? 0 : (int)samp_c;
+    if (part) {
+        const torch::Tensor &ages = st.ages, &slot_ages = st.slot_ages;
+        CHECK_DEV(perm); CHECK_DEV(pptr); CHECK_DEV(apart);
+        TORCH_CHECK(n_parts >= 1, "n_parts must be positive");
+        TORCH_CHECK(ages.numel() == ages.size(0) * n_parts &&
+                    slot_ages.numel() == slot_ages.size(0) * n_parts,
+                    "partitioned mlp: ages and slot_ages must be [*, n_parts]");
+        TORCH_CHECK(perm.numel() == a.D && apart.numel() == a.D &&
+                    pptr.numel() == n_parts + 1,
+                    "partition tables do not match the model row");
+        c.perm = perm.data_ptr<int>(); c.pptr = pptr.data_ptr<int>();
+        c.apart = apart.data_ptr<int>();
+    } else {
+        TORCH_CHECK(samp_c >= 1, "samp_c must be positive");
+    }
+    size_t w_slabs = (mode == MODE_MERGE_UPDATE) ? 1 : 2;
+    if (!part) {
+        c.w3_alias = (g.scratch >= (size_t)a.D) ? 1 : 0;
+        if (!c.w3_alias) w_slabs += 1;
+    }
+    L.smem = sizeof(float) * (w_slabs * (size_t)a.D + g.scratch) +
+             sizeof(int) * 2 * (size_t)c.P;
+    TORCH_CHECK(L.smem <= 160 * 1024, what, " mlp LDS budget exceeded (",
+                L.smem, " B > 163840 B); shrink batch_size/hidden, or use"
+                " MERGE_UPDATE (the other modes hold a second model slab)");
+    L.kernel = part ? tick_mlp_comp_kernel<true> : tick_mlp_comp_kernel<false>;
+    L.threads = g.threads;
+    // snapshots copy one age per partition
+    L.snap = {a.D, a.D, 0, part ? (int)n_parts : 1};
+    return L;
 }
 
-static void tick_mlp_comp(
-    bool part, torch::Tensor nodes, torch::Tensor recv_ptr,
-    torch::Tensor del_slots, torch::Tensor reply_slots, torch::Tensor del_pids,
-    bool update_only, MlpCompLaunch& L)
+// ---------------------------------------------------------------------------
+// tick entry points: one launch, one workgroup per receiving node
+// ---------------------------------------------------------------------------
+
+struct TickEvents {
+    torch::Tensor nodes, recv_ptr, del_slots, reply_slots;
+};
+
+template <typename Args>
+static void launch_tick(Plan<Args>& L, const TickEvents& ev, bool update_only,
+                        typename channel<Args>::type chan = nullptr,
+                        const torch::Tensor& chan_vals = {})
 {
+    const torch::Tensor &nodes = ev.nodes, &recv_ptr = ev.recv_ptr;
     int n = nodes.size(0);
     if (n == 0) return;
     CHECK_DEV(nodes); CHECK_DEV(recv_ptr);
-    L.c.m.nodes = nodes.data_ptr<int>(); L.c.m.ptr = recv_ptr.data_ptr<int>();
-    L.c.m.dslots = del_slots.numel() ? del_slots.data_ptr<int>() : nullptr;
-    L.c.m.rslots = reply_slots.numel() ? reply_slots.data_ptr<int>() : nullptr;
-    L.c.dpids = del_pids.numel() ? del_pids.data_ptr<int>() : nullptr;
-    L.c.m.update_only = update_only;
-    mlp_comp_launch(part, L, n, current_stream());
+    auto& e = events(L.a);
+    e.nodes = nodes.data_ptr<int>(); e.ptr = recv_ptr.data_ptr<int>();
+    e.dslots = iptr(ev.del_slots); e.rslots = iptr(ev.reply_slots);
+    e.update_only = update_only;
+    if (chan) L.a.*chan = iptr(chan_vals);
+    launch_kernel(L.kernel, n, L.threads, L.smem, current_stream(), L.a);
+}
+
+void tick_logreg(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
+                 torch::Tensor slot_ages, torch::Tensor nodes, torch::Tensor recv_ptr,
+                 torch::Tensor del_slots, torch::Tensor reply_slots,
+                 torch::Tensor X, torch::Tensor Y, torch::Tensor counts,
+                 int64_t d, int64_t k, double lr, double wd, int64_t epochs,
+                 int64_t bs, int64_t mode, bool update_only,
+                 torch::Tensor dmodes)
+{
+    auto L = logreg_plan({params, ages, slots, slot_ages, X, Y, counts},
+                         d, k, lr, wd, epochs, bs, mode);
+    launch_tick(L, {nodes, recv_ptr, del_slots, reply_slots}, update_only,
+                &LogregArgs::dmodes, dmodes);
+}
+
+void tick_linear(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
+                 torch::Tensor slot_ages, torch::Tensor nodes, torch::Tensor recv_ptr,
+                 torch::Tensor del_slots, torch::Tensor reply_slots,
+                 torch::Tensor X, torch::Tensor Y, torch::Tensor counts,
+                 int64_t d, double lrlam, int64_t is_pegasos, int64_t mode,
+                 bool update_only, torch::Tensor dmodes)
+{
+    auto L = linear_plan({params, ages, slots, slot_ages, X, Y, counts},
+                         d, lrlam, is_pegasos, mode);
+    launch_tick(L, {nodes, recv_ptr, del_slots, reply_slots}, update_only,
+                &LinearArgs::dmodes, dmodes);
+}
+
+void tick_mlp(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
+              torch::Tensor slot_ages, torch::Tensor nodes, torch::Tensor recv_ptr,
+              torch::Tensor del_slots, torch::Tensor reply_slots,
+              torch::Tensor X, torch::Tensor Y, torch::Tensor counts,
+              torch::Tensor layout, int64_t n_layers, double lr, double wd,
+              int64_t epochs, int64_t bs, int64_t mode, bool update_only,
+              torch::Tensor dmodes)
+{
+    auto L = mlp_plan({params, ages, slots, slot_ages, X, Y, counts},
+                      layout, n_layers, lr, wd, epochs, bs, mode);
+    launch_tick(L, {nodes, recv_ptr, del_slots, reply_slots}, update_only,
+                &MlpArgs::dmodes, dmodes);
+}
+
+void tick_logreg_part(
+    torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
+    torch::Tensor slot_ages, torch::Tensor nodes, torch::Tensor recv_ptr,
+    torch::Tensor del_slots, torch::Tensor reply_slots, torch::Tensor del_pids,
+    torch::Tensor X, torch::Tensor Y, torch::Tensor counts,
+    torch::Tensor perm, torch::Tensor pptr, torch::Tensor apart,
+    int64_t n_parts, int64_t d, int64_t k, double lr, double wd,
+    int64_t epochs, int64_t bs, int64_t mode, bool update_only)
+{
+    auto L = logreg_part_plan({params, ages, slots, slot_ages, X, Y, counts},
+                              perm, pptr, apart, n_parts, d, k, lr, wd,
+                              epochs, bs, mode);
+    launch_tick(L, {nodes, recv_ptr, del_slots, reply_slots}, update_only,
+                &LogregPartArgs::dpids, del_pids);
+}
+
+void tick_logreg_samp(
+    torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
+    torch::Tensor slot_ages, torch::Tensor nodes, torch::Tensor recv_ptr,
+    torch::Tensor del_slots, torch::Tensor reply_slots, torch::Tensor del_seeds,
+    torch::Tensor X, torch::Tensor Y, torch::Tensor counts,
+    int64_t samp_c, int64_t d, int64_t k, double lr, double wd,
+    int64_t epochs, int64_t bs, int64_t mode, bool update_only)
+{
+    auto L = logreg_samp_plan({params, ages, slots, slot_ages, X, Y, counts},
+                              samp_c, d, k, lr, wd, epochs, bs, mode);
+    launch_tick(L, {nodes, recv_ptr, del_slots, reply_slots}, update_only,
+                &LogregSampArgs::dseeds, del_seeds);
 }
 
 void tick_mlp_part(
@@ -2460,18 +2616,11 @@ void tick_mlp_part(
     int64_t n_parts, double lr, double wd, int64_t epochs, int64_t bs,
     int64_t mode, bool update_only)
 {
-    CHECK_DEV(perm); CHECK_DEV(pptr); CHECK_DEV(apart);
-    MlpCompLaunch L = mlp_comp_setup(
-        true, params, ages, slots, slot_ages, X, Y, counts, layout, n_layers,
-        n_parts, 0, lr, wd, epochs, bs, mode);
-    TORCH_CHECK(perm.numel() == params.size(1) &&
-                apart.numel() == params.size(1) &&
-                pptr.numel() == n_parts + 1,
-                "partition tables do not match the model row");
-    L.c.perm = perm.data_ptr<int>(); L.c.pptr = pptr.data_ptr<int>();
-    L.c.apart = apart.data_ptr<int>();
-    tick_mlp_comp(true, nodes, recv_ptr, del_slots, reply_slots, del_pids,
-                  update_only, L);
+    auto L = mlp_comp_plan(true, {params, ages, slots, slot_ages, X, Y, counts},
+                           layout, n_layers, perm, pptr, apart, n_parts, 0,
+                           lr, wd, epochs, bs, mode);
+    launch_tick(L, {nodes, recv_ptr, del_slots, reply_slots}, update_only,
+                &MlpCompArgs::dpids, del_pids);
 }
 
 void tick_mlp_samp(
@@ -2483,11 +2632,35 @@ void tick_mlp_samp(
     double lr, double wd, int64_t epochs, int64_t bs, int64_t mode,
     bool update_only)
 {
-    MlpCompLaunch L = mlp_comp_setup(
-        false, params, ages, slots, slot_ages, X, Y, counts, layout, n_layers,
-        0, samp_c, lr, wd, epochs, bs, mode);
-    tick_mlp_comp(false, nodes, recv_ptr, del_slots, reply_slots, del_seeds,
-                  update_only, L);
+    auto L = mlp_comp_plan(false, {params, ages, slots, slot_ages, X, Y, counts},
+                           layout, n_layers, {}, {}, {}, 0, samp_c,
+                           lr, wd, epochs, bs, mode);
+    launch_tick(L, {nodes, recv_ptr, del_slots, reply_slots}, update_only,
+                &MlpCompArgs::dpids, del_seeds);
+}
+
+void tick_mf(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
+             torch::Tensor slot_ages, torch::Tensor nodes, torch::Tensor recv_ptr,
+             torch::Tensor del_slots, torch::Tensor reply_slots,
+             torch::Tensor X, torch::Tensor Y, torch::Tensor counts,
+             int64_t k, int64_t n_items, double reg, double lr,
+             bool update_only)
+{
+    auto L = mf_plan({params, ages, slots, slot_ages, X, Y, counts},
+                     k, n_items, reg, lr);
+    launch_tick(L, {nodes, recv_ptr, del_slots, reply_slots}, update_only);
+}
+
+void tick_kmeans(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
+                 torch::Tensor slot_ages, torch::Tensor nodes,
+                 torch::Tensor recv_ptr, torch::Tensor del_slots,
+                 torch::Tensor reply_slots, torch::Tensor X,
+                 torch::Tensor counts, int64_t k, int64_t dim, double alpha,
+                 int64_t mode, bool update_only)
+{
+    auto L = kmeans_plan({params, ages, slots, slot_ages, X, {}, counts},
+                         k, dim, alpha, mode);
+    launch_tick(L, {nodes, recv_ptr, del_slots, reply_slots}, update_only);
 }
 
 // ---------------------------------------------------------------------------
@@ -2499,44 +2672,101 @@ void tick_mlp_samp(
 // ~200 launch enqueues of a few µs each.
 // ---------------------------------------------------------------------------
 
+// The leading parameters every run_round_* takes: the four state tensors,
+// the round's event arrays, then the data arena. del_pids / rep_pids carry
+// the partition ids (partitioned) or sample seeds (sampled) of each
+// delivery; the plain families ignore them.
+#define ROUND_PARAMS \
+    torch::Tensor params, torch::Tensor ages, torch::Tensor slots, \
+    torch::Tensor slot_ages, \
+    torch::Tensor snap_nodes, torch::Tensor snap_slots, torch::Tensor snap_tptr, \
+    torch::Tensor recv_nodes, torch::Tensor recv_nptr, torch::Tensor recv_tptr, \
+    torch::Tensor del_slots, torch::Tensor reply_slots, torch::Tensor del_pids, \
+    torch::Tensor pull_nodes, torch::Tensor pull_slots, torch::Tensor pull_tptr, \
+    torch::Tensor rep_nodes, torch::Tensor rep_nptr, torch::Tensor rep_tptr, \
+    torch::Tensor rep_slots, torch::Tensor rep_pids, \
+    torch::Tensor X, torch::Tensor Y, torch::Tensor counts
+#define ROUND_STATE {params, ages, slots, slot_ages, X, Y, counts}
+#define ROUND_EVENTS \
+    snap_nodes, snap_slots, snap_tptr, recv_nodes, recv_nptr, recv_tptr, \
+    del_slots, reply_slots, del_pids, pull_nodes, pull_slots, pull_tptr, \
+    rep_nodes, rep_nptr, rep_tptr, rep_slots, rep_pids
+
 struct RoundArrays {
     // device pointers
     const int *snap_nodes, *snap_slots;
     const int *recv_nodes, *recv_nptr;
-    const int *del_slots, *reply_slots;
+    const int *del_slots, *reply_slots, *del_pids;
     const int *pull_nodes, *pull_slots;
-    const int *rep_nodes, *rep_nptr, *rep_slots;
-    // host tick pointers [delta+1]
+    const int *rep_nodes, *rep_nptr, *rep_slots, *rep_pids, *rep_reply_slots;
+    // tick pointers [delta+1]: host-side for the stream executors,
+    // device-side for run_round_coop_logreg
     const int *snap_tptr, *recv_tptr, *pull_tptr, *rep_tptr;
+    torch::Tensor tptr_tensors[4];  // the same four, for the upload
     int delta;
 };
 
 static RoundArrays unpack_round(
     torch::Tensor snap_nodes, torch::Tensor snap_slots, torch::Tensor snap_tptr,
     torch::Tensor recv_nodes, torch::Tensor recv_nptr, torch::Tensor recv_tptr,
-    torch::Tensor del_slots, torch::Tensor reply_slots,
+    torch::Tensor del_slots, torch::Tensor reply_slots, torch::Tensor del_pids,
     torch::Tensor pull_nodes, torch::Tensor pull_slots, torch::Tensor pull_tptr,
     torch::Tensor rep_nodes, torch::Tensor rep_nptr, torch::Tensor rep_tptr,
-    torch::Tensor rep_slots)
+    torch::Tensor rep_slots, torch::Tensor rep_pids,
+    torch::Tensor rep_reply_slots)
 {
     RoundArrays r;
-    r.snap_nodes = snap_nodes.numel() ? snap_nodes.data_ptr<int>() : nullptr;
-    r.snap_slots = snap_slots.numel() ? snap_slots.data_ptr<int>() : nullptr;
-    r.recv_nodes = recv_nodes.numel() ? recv_nodes.data_ptr<int>() : nullptr;
-    r.recv_nptr = recv_nptr.data_ptr<int>();
-    r.del_slots = del_slots.numel() ? del_slots.data_ptr<int>() : nullptr;
-    r.reply_slots = reply_slots.numel() ? reply_slots.data_ptr<int>() : nullptr;
-    r.pull_nodes = pull_nodes.numel() ? pull_nodes.data_ptr<int>() : nullptr;
-    r.pull_slots = pull_slots.numel() ? pull_slots.data_ptr<int>() : nullptr;
-    r.rep_nodes = rep_nodes.numel() ? rep_nodes.data_ptr<int>() : nullptr;
-    r.rep_nptr = rep_nptr.data_ptr<int>();
-    r.rep_slots = rep_slots.numel() ? rep_slots.data_ptr<int>() : nullptr;
-    r.snap_tptr = snap_tptr.data_ptr<int>();   // host (CPU) tensors
+    r.snap_nodes = iptr(snap_nodes); r.snap_slots = iptr(snap_slots);
+    r.recv_nodes = iptr(recv_nodes); r.recv_nptr = recv_nptr.data_ptr<int>();
+    r.del_slots = iptr(del_slots); r.reply_slots = iptr(reply_slots);
+    r.del_pids = iptr(del_pids);
+    r.pull_nodes = iptr(pull_nodes); r.pull_slots = iptr(pull_slots);
+    r.rep_nodes = iptr(rep_nodes); r.rep_nptr = rep_nptr.data_ptr<int>();
+    r.rep_slots = iptr(rep_slots); r.rep_pids = iptr(rep_pids);
+    r.rep_reply_slots = iptr(rep_reply_slots);
+    r.snap_tptr = snap_tptr.data_ptr<int>();
     r.recv_tptr = recv_tptr.data_ptr<int>();
     r.pull_tptr = pull_tptr.data_ptr<int>();
     r.rep_tptr = rep_tptr.data_ptr<int>();
+    r.tptr_tensors[0] = snap_tptr; r.tptr_tensors[1] = recv_tptr;
+    r.tptr_tensors[2] = pull_tptr; r.tptr_tensors[3] = rep_tptr;
     r.delta = (int)snap_tptr.numel() - 1;
     return r;
+}
+
+// The one stream round loop: per tick snapshot, deliver, pull-snapshot,
+// reply-deliver. `chan` names the family's per-delivery pids/seeds member
+// (set from del_pids for deliveries, rep_pids for replies), or is null.
+template <typename Args>
+static void stream_round(Plan<Args>& L, const RoundArrays& r,
+                         typename channel<Args>::type chan = nullptr)
+{
+    hipStream_t s = current_stream();
+    auto& e = events(L.a);
+    auto snap = [&](const int* nodes, const int* slot_ids, int n) {
+        launch_snap(e.params, e.ages, e.slots, e.slot_ages, nodes, slot_ids,
+                    n, L.snap, s);
+    };
+    auto deliver = [&](const int* nodes, const int* nptr, int n,
+                       const int* dslots, const int* rslots, const int* pids) {
+        e.nodes = nodes; e.ptr = nptr; e.dslots = dslots; e.rslots = rslots;
+        if (chan) L.a.*chan = pids;
+        launch_kernel(L.kernel, n, L.threads, L.smem, s, L.a);
+    };
+    for (int t = 0; t < r.delta; ++t) {
+        int s0 = r.snap_tptr[t], s1 = r.snap_tptr[t + 1];
+        if (s1 > s0) snap(r.snap_nodes + s0, r.snap_slots + s0, s1 - s0);
+        int r0 = r.recv_tptr[t], r1 = r.recv_tptr[t + 1];
+        if (r1 > r0)
+            deliver(r.recv_nodes + r0, r.recv_nptr + r0, r1 - r0, r.del_slots,
+                    r.reply_slots, r.del_pids);
+        int p0 = r.pull_tptr[t], p1 = r.pull_tptr[t + 1];
+        if (p1 > p0) snap(r.pull_nodes + p0, r.pull_slots + p0, p1 - p0);
+        int q0 = r.rep_tptr[t], q1 = r.rep_tptr[t + 1];
+        if (q1 > q0)
+            deliver(r.rep_nodes + q0, r.rep_nptr + q0, q1 - q0, r.rep_slots,
+                    r.rep_reply_slots, r.rep_pids);
+    }
 }
 
 static int sb_threshold()
@@ -2562,589 +2792,189 @@ static int max_group(const RoundArrays& r)
     return mx;
 }
 
-static void launch_snap(const float* params, const int* ages, float* slots,
-                        int* slot_ages, const int* nodes, const int* slot_ids,
-                        int n, int D, hipStream_t s, int A = 1)
+static void set_pids(PartRoundArgs& c, const RoundArrays& r)
 {
-    long total = (long)n * D;
-    int block = 256;
-    int grid = (int)std::min<long>((total + block - 1) / block, 2048);
-    hipLaunchKernelGGL(snapshot_kernel, dim3(grid), dim3(block), 0, s,
-                       params, ages, slots, slot_ages, nodes, slot_ids, n, D,
-                       D, 0, A);
+    c.del_pids = r.del_pids; c.rep_pids = r.rep_pids;
+}
+template <typename RoundArgs> static void set_pids(RoundArgs&, const RoundArrays&) {}
+
+// Fills a whole-round kernel's args (CoopRoundArgs, LinRoundArgs and
+// PartRoundArgs share their field names) from the plan's base args and the
+// round's arrays. The four tick pointers must be device-resident here.
+template <typename RoundArgs, typename Args>
+static RoundArgs round_args(const Args& base, const RoundArrays& r,
+                            const int* snap_tptr, const int* recv_tptr,
+                            const int* pull_tptr, const int* rep_tptr)
+{
+    RoundArgs c;
+    c.base = base;
+    c.snap_nodes = r.snap_nodes; c.snap_slots = r.snap_slots;
+    c.snap_tptr = snap_tptr;
+    c.recv_nodes = r.recv_nodes; c.recv_nptr = r.recv_nptr;
+    c.recv_tptr = recv_tptr;
+    c.del_slots = r.del_slots; c.reply_slots = r.reply_slots;
+    c.pull_nodes = r.pull_nodes; c.pull_slots = r.pull_slots;
+    c.pull_tptr = pull_tptr;
+    c.rep_nodes = r.rep_nodes; c.rep_nptr = r.rep_nptr;
+    c.rep_tptr = rep_tptr;
+    c.rep_slots = r.rep_slots;
+    set_pids(c, r);
+    c.delta = r.delta;
+    return c;
+}
+
+// Single-workgroup fallback for tiny batches: the family's whole-round
+// kernel launched PLAIN with one workgroup (in the coop kernel round_sync
+// degrades to __syncthreads) — one launch for the round. Returns false,
+// having done nothing, when the round does not qualify.
+template <typename RoundArgs, typename Args>
+static bool single_block_round(void (*kernel)(RoundArgs), const Plan<Args>& L,
+                               const RoundArrays& r, torch::Device dev)
+{
+    if (!(max_group(r) <= sb_threshold() && r.rep_reply_slots == nullptr))
+        return false;
+    torch::Tensor t[4];
+    for (int i = 0; i < 4; ++i) t[i] = r.tptr_tensors[i].to(dev);
+    RoundArgs c = round_args<RoundArgs>(
+        L.a, r, t[0].data_ptr<int>(), t[1].data_ptr<int>(),
+        t[2].data_ptr<int>(), t[3].data_ptr<int>());
+    launch_kernel(kernel, 1, L.threads, L.smem, current_stream(), c);
+    // keep the uploaded tptr tensors alive past the async launch
+    static thread_local std::vector<torch::Tensor> keep;
+    keep.insert(keep.end(), t, t + 4);
+    if (keep.size() > 64) keep.erase(keep.begin(), keep.begin() + 32);
+    return true;
 }
 
 void run_round_logreg(
-    torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
-    torch::Tensor slot_ages,
-    torch::Tensor snap_nodes, torch::Tensor snap_slots, torch::Tensor snap_tptr,
-    torch::Tensor recv_nodes, torch::Tensor recv_nptr, torch::Tensor recv_tptr,
-    torch::Tensor del_slots, torch::Tensor reply_slots,
-    torch::Tensor pull_nodes, torch::Tensor pull_slots, torch::Tensor pull_tptr,
-    torch::Tensor rep_nodes, torch::Tensor rep_nptr, torch::Tensor rep_tptr,
-    torch::Tensor rep_slots,
-    torch::Tensor X, torch::Tensor Y, torch::Tensor counts,
+    ROUND_PARAMS,
     int64_t d, int64_t k, double lr, double wd, int64_t epochs, int64_t bs,
-    int64_t mode,
-    torch::Tensor rep_reply_slots)
+    int64_t mode, torch::Tensor rep_reply_slots)
 {
-    CHECK_DEV(params); CHECK_DEV(slots); CHECK_DEV(X);
-    RoundArrays r = unpack_round(snap_nodes, snap_slots, snap_tptr, recv_nodes,
-                                 recv_nptr, recv_tptr, del_slots, reply_slots,
-                                 pull_nodes, pull_slots, pull_tptr, rep_nodes,
-                                 rep_nptr, rep_tptr, rep_slots);
-    const int* rep_rr =
-        (rep_reply_slots.defined() && rep_reply_slots.numel())
-            ? rep_reply_slots.data_ptr<int>() : nullptr;
-    hipStream_t s = current_stream();
-    LogregArgs a;
-    a.params = params.data_ptr<float>(); a.ages = ages.data_ptr<int>();
-    a.slots = slots.data_ptr<float>(); a.slot_ages = slot_ages.data_ptr<int>();
-    a.X = X.data_ptr<float>(); a.Y = Y.data_ptr<float>();
-    a.counts = counts.data_ptr<int>();
-    a.dmodes = nullptr;
-    a.d = d; a.k = k; a.Smax = X.size(1); a.D = params.size(1);
-    a.lr = lr; a.wd = wd; a.epochs = epochs; a.bs = bs; a.mode = mode;
-    a.update_only = 0;
-    int bsmax = (bs == 0) ? a.Smax : std::min<int>(bs, a.Smax);
-    size_t smem = sizeof(float) * (2 * a.D + (size_t)bsmax * a.d + (size_t)bsmax * a.k);
-    TORCH_CHECK(smem <= 160 * 1024, "logreg LDS budget exceeded");
-    if (max_group(r) <= sb_threshold() && rep_rr == nullptr) {
-        // tiny batches: the coop round kernel launched PLAIN with one
-        // workgroup (round_sync degrades to __syncthreads)
-        auto dev = params.device();
-        auto st = snap_tptr.to(dev), rt = recv_tptr.to(dev);
-        auto pt = pull_tptr.to(dev), qt = rep_tptr.to(dev);
-        CoopRoundArgs c;
-        c.base = a;
-        c.snap_nodes = r.snap_nodes; c.snap_slots = r.snap_slots;
-        c.snap_tptr = st.data_ptr<int>();
-        c.recv_nodes = r.recv_nodes; c.recv_nptr = r.recv_nptr;
-        c.recv_tptr = rt.data_ptr<int>();
-        c.del_slots = r.del_slots; c.reply_slots = r.reply_slots;
-        c.pull_nodes = r.pull_nodes; c.pull_slots = r.pull_slots;
-        c.pull_tptr = pt.data_ptr<int>();
-        c.rep_nodes = r.rep_nodes; c.rep_nptr = r.rep_nptr;
-        c.rep_tptr = qt.data_ptr<int>();
-        c.rep_slots = r.rep_slots;
-        c.delta = r.delta;
-        hipLaunchKernelGGL(coop_round_logreg_kernel, dim3(1), dim3(128),
-                           smem, s, c);
-        static thread_local std::vector<torch::Tensor> keep;
-        keep.insert(keep.end(), {st, rt, pt, qt});
-        if (keep.size() > 64) keep.erase(keep.begin(), keep.begin() + 32);
+    auto L = logreg_plan(ROUND_STATE, d, k, lr, wd, epochs, bs, mode);
+    RoundArrays r = unpack_round(ROUND_EVENTS, rep_reply_slots);
+    if (single_block_round(coop_round_logreg_kernel, L, r, params.device()))
         return;
-    }
-    for (int t = 0; t < r.delta; ++t) {
-        int s0 = r.snap_tptr[t], s1 = r.snap_tptr[t + 1];
-        if (s1 > s0)
-            launch_snap(a.params, a.ages, a.slots, a.slot_ages,
-                        r.snap_nodes + s0, r.snap_slots + s0, s1 - s0, a.D, s);
-        int r0 = r.recv_tptr[t], r1 = r.recv_tptr[t + 1];
-        if (r1 > r0) {
-            a.nodes = r.recv_nodes + r0;
-            a.ptr = r.recv_nptr + r0;
-            a.dslots = r.del_slots;
-            a.rslots = r.reply_slots;
-            hipLaunchKernelGGL(tick_logreg_kernel, dim3(r1 - r0), dim3(128),
-                               smem, s, a);
-        }
-        int p0 = r.pull_tptr[t], p1 = r.pull_tptr[t + 1];
-        if (p1 > p0)
-            launch_snap(a.params, a.ages, a.slots, a.slot_ages,
-                        r.pull_nodes + p0, r.pull_slots + p0, p1 - p0, a.D, s);
-        int q0 = r.rep_tptr[t], q1 = r.rep_tptr[t + 1];
-        if (q1 > q0) {
-            a.nodes = r.rep_nodes + q0;
-            a.ptr = r.rep_nptr + q0;
-            a.dslots = r.rep_slots;
-            a.rslots = rep_rr;
-            hipLaunchKernelGGL(tick_logreg_kernel, dim3(q1 - q0), dim3(128),
-                               smem, s, a);
-        }
-    }
+    stream_round(L, r);
 }
 
 void run_round_linear(
-    torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
-    torch::Tensor slot_ages,
-    torch::Tensor snap_nodes, torch::Tensor snap_slots, torch::Tensor snap_tptr,
-    torch::Tensor recv_nodes, torch::Tensor recv_nptr, torch::Tensor recv_tptr,
-    torch::Tensor del_slots, torch::Tensor reply_slots,
-    torch::Tensor pull_nodes, torch::Tensor pull_slots, torch::Tensor pull_tptr,
-    torch::Tensor rep_nodes, torch::Tensor rep_nptr, torch::Tensor rep_tptr,
-    torch::Tensor rep_slots,
-    torch::Tensor X, torch::Tensor Y, torch::Tensor counts,
+    ROUND_PARAMS,
     int64_t d, double lrlam, int64_t is_pegasos, int64_t mode,
     torch::Tensor rep_reply_slots)
 {
-    CHECK_DEV(params); CHECK_DEV(slots); CHECK_DEV(X);
-    RoundArrays r = unpack_round(snap_nodes, snap_slots, snap_tptr, recv_nodes,
-                                 recv_nptr, recv_tptr, del_slots, reply_slots,
-                                 pull_nodes, pull_slots, pull_tptr, rep_nodes,
-                                 rep_nptr, rep_tptr, rep_slots);
-    const int* rep_rr =
-        (rep_reply_slots.defined() && rep_reply_slots.numel())
-            ? rep_reply_slots.data_ptr<int>() : nullptr;
-    hipStream_t s = current_stream();
-    LinearArgs a;
-    a.params = params.data_ptr<float>(); a.ages = ages.data_ptr<int>();
-    a.slots = slots.data_ptr<float>(); a.slot_ages = slot_ages.data_ptr<int>();
-    a.X = X.data_ptr<float>(); a.Y = Y.data_ptr<float>();
-    a.counts = counts.data_ptr<int>();
-    a.dmodes = nullptr;
-    a.d = d; a.Smax = X.size(1);
-    a.lrlam = lrlam; a.is_pegasos = is_pegasos; a.mode = mode;
-    a.update_only = 0;
-    if (max_group(r) <= sb_threshold() && rep_rr == nullptr) {
-        // tiny batches: one plain single-workgroup launch for the round
-        auto dev = params.device();
-        auto st = snap_tptr.to(dev), rt = recv_tptr.to(dev);
-        auto pt = pull_tptr.to(dev), qt = rep_tptr.to(dev);
-        LinRoundArgs c;
-        c.base = a;
-        c.snap_nodes = r.snap_nodes; c.snap_slots = r.snap_slots;
-        c.snap_tptr = st.data_ptr<int>();
-        c.recv_nodes = r.recv_nodes; c.recv_nptr = r.recv_nptr;
-        c.recv_tptr = rt.data_ptr<int>();
-        c.del_slots = r.del_slots; c.reply_slots = r.reply_slots;
-        c.pull_nodes = r.pull_nodes; c.pull_slots = r.pull_slots;
-        c.pull_tptr = pt.data_ptr<int>();
-        c.rep_nodes = r.rep_nodes; c.rep_nptr = r.rep_nptr;
-        c.rep_tptr = qt.data_ptr<int>();
-        c.rep_slots = r.rep_slots;
-        c.delta = r.delta;
-        hipLaunchKernelGGL(sb_round_linear_kernel, dim3(1), dim3(WAVE), 0, s, c);
-        // keep the uploaded tptr tensors alive past the async launch
-        static thread_local std::vector<torch::Tensor> keep;
-        keep.insert(keep.end(), {st, rt, pt, qt});
-        if (keep.size() > 64) keep.erase(keep.begin(), keep.begin() + 32);
+    auto L = linear_plan(ROUND_STATE, d, lrlam, is_pegasos, mode);
+    RoundArrays r = unpack_round(ROUND_EVENTS, rep_reply_slots);
+    if (single_block_round(sb_round_linear_kernel, L, r, params.device()))
         return;
-    }
-    for (int t = 0; t < r.delta; ++t) {
-        int s0 = r.snap_tptr[t], s1 = r.snap_tptr[t + 1];
-        if (s1 > s0)
-            launch_snap(a.params, a.ages, a.slots, a.slot_ages,
-                        r.snap_nodes + s0, r.snap_slots + s0, s1 - s0, a.d, s);
-        int r0 = r.recv_tptr[t], r1 = r.recv_tptr[t + 1];
-        if (r1 > r0) {
-            a.nodes = r.recv_nodes + r0;
-            a.ptr = r.recv_nptr + r0;
-            a.dslots = r.del_slots;
-            a.rslots = r.reply_slots;
-            hipLaunchKernelGGL(tick_linear_kernel, dim3(r1 - r0), dim3(WAVE),
-                               0, s, a);
-        }
-        int p0 = r.pull_tptr[t], p1 = r.pull_tptr[t + 1];
-        if (p1 > p0)
-            launch_snap(a.params, a.ages, a.slots, a.slot_ages,
-                        r.pull_nodes + p0, r.pull_slots + p0, p1 - p0, a.d, s);
-        int q0 = r.rep_tptr[t], q1 = r.rep_tptr[t + 1];
-        if (q1 > q0) {
-            a.nodes = r.rep_nodes + q0;
-            a.ptr = r.rep_nptr + q0;
-            a.dslots = r.rep_slots;
-            a.rslots = rep_rr;
-            hipLaunchKernelGGL(tick_linear_kernel, dim3(q1 - q0), dim3(WAVE),
-                               0, s, a);
-        }
-    }
-}
-
-void tick_logreg_samp(
-    torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
-    torch::Tensor slot_ages, torch::Tensor nodes, torch::Tensor recv_ptr,
-    torch::Tensor del_slots, torch::Tensor reply_slots, torch::Tensor del_seeds,
-    torch::Tensor X, torch::Tensor Y, torch::Tensor counts,
-    int64_t samp_c, int64_t d, int64_t k, double lr, double wd,
-    int64_t epochs, int64_t bs, int64_t mode, bool update_only)
-{
-    CHECK_DEV(params); CHECK_DEV(slots); CHECK_DEV(X); CHECK_DEV(Y);
-    TORCH_CHECK(k <= KMAX, "n_classes > ", KMAX, " unsupported");
-    TORCH_CHECK(mode != MODE_PASS, "Mode PASS not allowed for sampled models.");
-    int n = nodes.size(0);
-    if (n == 0) return;
-    LogregSampArgs a;
-    a.params = params.data_ptr<float>(); a.ages = ages.data_ptr<int>();
-    a.slots = slots.data_ptr<float>(); a.slot_ages = slot_ages.data_ptr<int>();
-    a.nodes = nodes.data_ptr<int>(); a.ptr = recv_ptr.data_ptr<int>();
-    a.dslots = del_slots.numel() ? del_slots.data_ptr<int>() : nullptr;
-    a.rslots = reply_slots.numel() ? reply_slots.data_ptr<int>() : nullptr;
-    a.dseeds = del_seeds.numel() ? del_seeds.data_ptr<int>() : nullptr;
-    a.X = X.data_ptr<float>(); a.Y = Y.data_ptr<float>();
-    a.counts = counts.data_ptr<int>();
-    a.samp_c = samp_c; a.d = d; a.k = k; a.Smax = X.size(1);
-    a.D = params.size(1);
-    a.lr = lr; a.wd = wd; a.epochs = epochs; a.bs = bs; a.mode = mode;
-    a.update_only = update_only;
-    int bsmax = (bs == 0) ? a.Smax : std::min<int>(bs, a.Smax);
-    size_t smem = sizeof(float) * (3 * a.D + (size_t)bsmax * a.d +
-                                   (size_t)bsmax * a.k);
-    TORCH_CHECK(smem <= 160 * 1024, "sampled logreg LDS budget exceeded: ", smem);
-    hipLaunchKernelGGL(tick_logreg_samp_kernel, dim3(n), dim3(128), smem,
-                       current_stream(), a);
-}
-
-void tick_mf(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
-             torch::Tensor slot_ages, torch::Tensor nodes, torch::Tensor recv_ptr,
-             torch::Tensor del_slots, torch::Tensor reply_slots,
-             torch::Tensor X, torch::Tensor Y, torch::Tensor counts,
-             int64_t k, int64_t n_items, double reg, double lr,
-             bool update_only)
-{
-    CHECK_DEV(params); CHECK_DEV(slots); CHECK_DEV(X); CHECK_DEV(Y);
-    TORCH_CHECK(k <= WAVE, "MF latent dim > ", WAVE, " unsupported");
-    int n = nodes.size(0);
-    if (n == 0) return;
-    MFArgs a;
-    a.params = params.data_ptr<float>(); a.ages = ages.data_ptr<int>();
-    a.slots = slots.data_ptr<float>(); a.slot_ages = slot_ages.data_ptr<int>();
-    a.nodes = nodes.data_ptr<int>(); a.ptr = recv_ptr.data_ptr<int>();
-    a.dslots = del_slots.numel() ? del_slots.data_ptr<int>() : nullptr;
-    a.rslots = reply_slots.numel() ? reply_slots.data_ptr<int>() : nullptr;
-    a.X = X.data_ptr<float>(); a.Y = Y.data_ptr<float>();
-    a.counts = counts.data_ptr<int>();
-    a.k = k; a.n_items = n_items; a.Smax = X.size(1); a.D = params.size(1);
-    a.item_off = k + 1; a.Wslot = n_items * (k + 1);
-    a.reg = reg; a.lr = lr; a.update_only = update_only;
-    hipLaunchKernelGGL(tick_mf_kernel, dim3(n), dim3(256), 0,
-                       current_stream(), a);
-}
-
-void tick_kmeans(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
-                 torch::Tensor slot_ages, torch::Tensor nodes,
-                 torch::Tensor recv_ptr, torch::Tensor del_slots,
-                 torch::Tensor reply_slots, torch::Tensor X,
-                 torch::Tensor counts, int64_t k, int64_t dim, double alpha,
-                 int64_t mode, bool update_only)
-{
-    CHECK_DEV(params); CHECK_DEV(slots); CHECK_DEV(X);
-    int n = nodes.size(0);
-    if (n == 0) return;
-    KMeansArgs a;
-    a.params = params.data_ptr<float>(); a.ages = ages.data_ptr<int>();
-    a.slots = slots.data_ptr<float>(); a.slot_ages = slot_ages.data_ptr<int>();
-    a.nodes = nodes.data_ptr<int>(); a.ptr = recv_ptr.data_ptr<int>();
-    a.dslots = del_slots.numel() ? del_slots.data_ptr<int>() : nullptr;
-    a.rslots = reply_slots.numel() ? reply_slots.data_ptr<int>() : nullptr;
-    a.X = X.data_ptr<float>(); a.counts = counts.data_ptr<int>();
-    a.k = k; a.dim = dim; a.Smax = X.size(1); a.D = params.size(1);
-    a.alpha = alpha; a.mode = mode; a.update_only = update_only;
-    size_t smem = sizeof(float) * 2 * a.D + sizeof(int) * a.Smax;
-    TORCH_CHECK(smem <= 160 * 1024, "kmeans LDS budget exceeded: ", smem);
-    hipLaunchKernelGGL(tick_kmeans_kernel, dim3(n), dim3(128), smem,
-                       current_stream(), a);
+    stream_round(L, r);
 }
 
 void run_round_logreg_part(
-    torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
-    torch::Tensor slot_ages,
-    torch::Tensor snap_nodes, torch::Tensor snap_slots, torch::Tensor snap_tptr,
-    torch::Tensor recv_nodes, torch::Tensor recv_nptr, torch::Tensor recv_tptr,
-    torch::Tensor del_slots, torch::Tensor reply_slots, torch::Tensor del_pids,
-    torch::Tensor pull_nodes, torch::Tensor pull_slots, torch::Tensor pull_tptr,
-    torch::Tensor rep_nodes, torch::Tensor rep_nptr, torch::Tensor rep_tptr,
-    torch::Tensor rep_slots, torch::Tensor rep_pids,
-    torch::Tensor X, torch::Tensor Y, torch::Tensor counts,
+    ROUND_PARAMS,
     torch::Tensor perm, torch::Tensor pptr, torch::Tensor apart,
     int64_t n_parts, int64_t d, int64_t k, double lr, double wd,
-    int64_t epochs, int64_t bs, int64_t mode,
-    torch::Tensor rep_reply_slots)
+    int64_t epochs, int64_t bs, int64_t mode, torch::Tensor rep_reply_slots)
 {
-    CHECK_DEV(params); CHECK_DEV(slots); CHECK_DEV(X);
-    CHECK_DEV(perm); CHECK_DEV(pptr); CHECK_DEV(apart);
-    TORCH_CHECK(mode != MODE_PASS, "Mode PASS not allowed for partitioned models.");
-    RoundArrays r = unpack_round(snap_nodes, snap_slots, snap_tptr, recv_nodes,
-                                 recv_nptr, recv_tptr, del_slots, reply_slots,
-                                 pull_nodes, pull_slots, pull_tptr, rep_nodes,
-                                 rep_nptr, rep_tptr, rep_slots);
-    const int* d_pids = del_pids.numel() ? del_pids.data_ptr<int>() : nullptr;
-    const int* r_pids = rep_pids.numel() ? rep_pids.data_ptr<int>() : nullptr;
-    const int* rep_rr =
-        (rep_reply_slots.defined() && rep_reply_slots.numel())
-            ? rep_reply_slots.data_ptr<int>() : nullptr;
-    hipStream_t s = current_stream();
-    LogregPartArgs a;
-    a.params = params.data_ptr<float>(); a.ages = ages.data_ptr<int>();
-    a.slots = slots.data_ptr<float>(); a.slot_ages = slot_ages.data_ptr<int>();
-    a.X = X.data_ptr<float>(); a.Y = Y.data_ptr<float>();
-    a.counts = counts.data_ptr<int>();
-    a.perm = perm.data_ptr<int>(); a.pptr = pptr.data_ptr<int>();
-    a.apart = apart.data_ptr<int>();
-    a.P = n_parts; a.d = d; a.k = k; a.Smax = X.size(1); a.D = params.size(1);
-    a.lr = lr; a.wd = wd; a.epochs = epochs; a.bs = bs; a.mode = mode;
-    a.update_only = 0;
-    int bsmax = (bs == 0) ? a.Smax : std::min<int>(bs, a.Smax);
-    size_t full = sizeof(float) * (2 * a.D + (size_t)a.Smax * a.d +
-                                   (size_t)bsmax * a.k) +
-                  sizeof(int) * 2 * a.P;
-    a.stage_full = (full <= 64 * 1024) ? 1 : 0;
-    size_t smem = a.stage_full
-        ? full
-        : sizeof(float) * (2 * a.D + (size_t)bsmax * a.d +
-                           (size_t)bsmax * a.k) +
-              sizeof(int) * 2 * a.P;
-    TORCH_CHECK(smem <= 160 * 1024, "partitioned logreg LDS budget exceeded");
-    if (max_group(r) <= sb_threshold() && rep_rr == nullptr) {
-        auto dev = params.device();
-        auto st = snap_tptr.to(dev), rt = recv_tptr.to(dev);
-        auto pt = pull_tptr.to(dev), qt = rep_tptr.to(dev);
-        PartRoundArgs c;
-        c.base = a;
-        c.snap_nodes = r.snap_nodes; c.snap_slots = r.snap_slots;
-        c.snap_tptr = st.data_ptr<int>();
-        c.recv_nodes = r.recv_nodes; c.recv_nptr = r.recv_nptr;
-        c.recv_tptr = rt.data_ptr<int>();
-        c.del_slots = r.del_slots; c.reply_slots = r.reply_slots;
-        c.del_pids = d_pids;
-        c.pull_nodes = r.pull_nodes; c.pull_slots = r.pull_slots;
-        c.pull_tptr = pt.data_ptr<int>();
-        c.rep_nodes = r.rep_nodes; c.rep_nptr = r.rep_nptr;
-        c.rep_tptr = qt.data_ptr<int>();
-        c.rep_slots = r.rep_slots;
-        c.rep_pids = r_pids;
-        c.delta = r.delta;
-        hipLaunchKernelGGL(sb_round_logreg_part_kernel, dim3(1), dim3(128),
-                           smem, s, c);
-        static thread_local std::vector<torch::Tensor> keep;
-        keep.insert(keep.end(), {st, rt, pt, qt});
-        if (keep.size() > 64) keep.erase(keep.begin(), keep.begin() + 32);
+    auto L = logreg_part_plan(ROUND_STATE, perm, pptr, apart, n_parts, d, k,
+                              lr, wd, epochs, bs, mode);
+    RoundArrays r = unpack_round(ROUND_EVENTS, rep_reply_slots);
+    if (single_block_round(sb_round_logreg_part_kernel, L, r, params.device()))
         return;
-    }
-    for (int t = 0; t < r.delta; ++t) {
-        int s0 = r.snap_tptr[t], s1 = r.snap_tptr[t + 1];
-        if (s1 > s0)
-            launch_snap(a.params, a.ages, a.slots, a.slot_ages,
-                        r.snap_nodes + s0, r.snap_slots + s0, s1 - s0, a.D, s,
-                        a.P);
-        int r0 = r.recv_tptr[t], r1 = r.recv_tptr[t + 1];
-        if (r1 > r0) {
-            a.nodes = r.recv_nodes + r0;
-            a.ptr = r.recv_nptr + r0;
-            a.dslots = r.del_slots;
-            a.rslots = r.reply_slots;
-            a.dpids = d_pids;
-            hipLaunchKernelGGL(tick_logreg_part_kernel, dim3(r1 - r0), dim3(128),
-                               smem, s, a);
-        }
-        int p0 = r.pull_tptr[t], p1 = r.pull_tptr[t + 1];
-        if (p1 > p0)
-            launch_snap(a.params, a.ages, a.slots, a.slot_ages,
-                        r.pull_nodes + p0, r.pull_slots + p0, p1 - p0, a.D, s,
-                        a.P);
-        int q0 = r.rep_tptr[t], q1 = r.rep_tptr[t + 1];
-        if (q1 > q0) {
-            a.nodes = r.rep_nodes + q0;
-            a.ptr = r.rep_nptr + q0;
-            a.dslots = r.rep_slots;
-            a.rslots = rep_rr;
-            a.dpids = r_pids;
-            hipLaunchKernelGGL(tick_logreg_part_kernel, dim3(q1 - q0), dim3(128),
-                               smem, s, a);
-        }
-    }
+    stream_round(L, r, &LogregPartArgs::dpids);
+}
+
+void run_round_logreg_samp(
+    ROUND_PARAMS,
+    int64_t samp_c, int64_t d, int64_t k, double lr, double wd,
+    int64_t epochs, int64_t bs, int64_t mode, torch::Tensor rep_reply_slots)
+{
+    auto L = logreg_samp_plan(ROUND_STATE, samp_c, d, k, lr, wd, epochs, bs,
+                              mode);
+    RoundArrays r = unpack_round(ROUND_EVENTS, rep_reply_slots);
+    stream_round(L, r, &LogregSampArgs::dseeds);
 }
 
 void run_round_mlp(
-    torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
-    torch::Tensor slot_ages,
-    torch::Tensor snap_nodes, torch::Tensor snap_slots, torch::Tensor snap_tptr,
-    torch::Tensor recv_nodes, torch::Tensor recv_nptr, torch::Tensor recv_tptr,
-    torch::Tensor del_slots, torch::Tensor reply_slots,
-    torch::Tensor pull_nodes, torch::Tensor pull_slots, torch::Tensor pull_tptr,
-    torch::Tensor rep_nodes, torch::Tensor rep_nptr, torch::Tensor rep_tptr,
-    torch::Tensor rep_slots,
-    torch::Tensor X, torch::Tensor Y, torch::Tensor counts,
+    ROUND_PARAMS,
     torch::Tensor layout, int64_t n_layers, double lr, double wd,
-    int64_t epochs, int64_t bs, int64_t mode,
-    torch::Tensor rep_reply_slots)
+    int64_t epochs, int64_t bs, int64_t mode, torch::Tensor rep_reply_slots)
 {
-    CHECK_DEV(params); CHECK_DEV(slots); CHECK_DEV(X); CHECK_DEV(layout);
-    RoundArrays r = unpack_round(snap_nodes, snap_slots, snap_tptr, recv_nodes,
-                                 recv_nptr, recv_tptr, del_slots, reply_slots,
-                                 pull_nodes, pull_slots, pull_tptr, rep_nodes,
-                                 rep_nptr, rep_tptr, rep_slots);
-    const int* rep_rr =
-        (rep_reply_slots.defined() && rep_reply_slots.numel())
-            ? rep_reply_slots.data_ptr<int>() : nullptr;
-    hipStream_t s = current_stream();
-    MlpArgs a;
-    a.params = params.data_ptr<float>(); a.ages = ages.data_ptr<int>();
-    a.slots = slots.data_ptr<float>(); a.slot_ages = slot_ages.data_ptr<int>();
-    a.X = X.data_ptr<float>(); a.Y = Y.data_ptr<float>();
-    a.counts = counts.data_ptr<int>();
-    a.layout = layout.data_ptr<int>();
-    a.dmodes = nullptr;
-    a.n_layers = n_layers; a.Smax = X.size(1); a.D = params.size(1);
-    a.lr = lr; a.wd = wd; a.epochs = epochs; a.bs = bs; a.mode = mode;
-    a.update_only = 0;
-    auto lay = layout.cpu();
-    const int* L = lay.data_ptr<int>();
-    int act_sum = 0, act_max = L[2];
-    for (int l = 0; l < n_layers; ++l) {
-        act_sum += L[4 * l + 3];
-        act_max = std::max(act_max, L[4 * l + 3]);
-        act_max = std::max(act_max, L[4 * l + 2]);
-    }
-    a.act_max = act_max;
-    a.d_in = L[2];
-    int bsmax = (bs == 0) ? a.Smax : std::min<int>(bs, a.Smax);
-    size_t w_slabs = (mode == MODE_UPDATE_MERGE) ? 2 : 1;  // W2 only there
-    size_t smem = sizeof(float) *
-        (w_slabs * (size_t)a.D + (size_t)bsmax * (a.d_in + act_sum) +
-         2 * (size_t)bsmax * act_max);
-    TORCH_CHECK(smem <= 160 * 1024, "mlp LDS budget exceeded");
-    // 8 waves when any GEMM stage has >= 8 MFMA tiles (same policy as
-    // tick_mlp — the packed executor previously hardcoded 4 waves, which
-    // left each SIMD with a single wave and every LDS/MFMA stall exposed)
-    int max_tiles = 0;
-    {
-        int m16 = (bsmax + 15) >> 4;
-        for (int l = 0; l < n_layers; ++l) {
-            int fin16 = (L[4 * l + 2] + 15) >> 4;
-            int fout16 = (L[4 * l + 3] + 15) >> 4;
-            max_tiles = std::max(max_tiles, m16 * fout16);
-            max_tiles = std::max(max_tiles, m16 * fin16);
-            max_tiles = std::max(max_tiles, fout16 * fin16);
-        }
-    }
-    int threads = (max_tiles >= 8) ? 512 : 256;
-    for (int t = 0; t < r.delta; ++t) {
-        int s0 = r.snap_tptr[t], s1 = r.snap_tptr[t + 1];
-        if (s1 > s0)
-            launch_snap(a.params, a.ages, a.slots, a.slot_ages,
-                        r.snap_nodes + s0, r.snap_slots + s0, s1 - s0, a.D, s);
-        int r0 = r.recv_tptr[t], r1 = r.recv_tptr[t + 1];
-        if (r1 > r0) {
-            a.nodes = r.recv_nodes + r0;
-            a.ptr = r.recv_nptr + r0;
-            a.dslots = r.del_slots;
-            a.rslots = r.reply_slots;
-            hipLaunchKernelGGL(tick_mlp_kernel, dim3(r1 - r0),
-                               dim3(threads), smem, s, a);
-        }
-        int p0 = r.pull_tptr[t], p1 = r.pull_tptr[t + 1];
-        if (p1 > p0)
-            launch_snap(a.params, a.ages, a.slots, a.slot_ages,
-                        r.pull_nodes + p0, r.pull_slots + p0, p1 - p0, a.D, s);
-        int q0 = r.rep_tptr[t], q1 = r.rep_tptr[t + 1];
-        if (q1 > q0) {
-            a.nodes = r.rep_nodes + q0;
-            a.ptr = r.rep_nptr + q0;
-            a.dslots = r.rep_slots;
-            a.rslots = rep_rr;
-            hipLaunchKernelGGL(tick_mlp_kernel, dim3(q1 - q0),
-                               dim3(threads), smem, s, a);
-        }
-    }
-}
-
-// The tick loop of run_round_mlp for the compressed kernels: del_pids /
-// rep_pids carry the partition ids (partitioned) or sample seeds (sampled),
-// and snapshots copy A ages per row.
-static void run_round_mlp_comp(bool part, MlpCompLaunch& L,
-                               const RoundArrays& r, const int* d_pids,
-                               const int* r_pids, const int* rep_rr, int A)
-{
-    hipStream_t s = current_stream();
-    MlpArgs& a = L.c.m;
-    for (int t = 0; t < r.delta; ++t) {
-        int s0 = r.snap_tptr[t], s1 = r.snap_tptr[t + 1];
-        if (s1 > s0)
-            launch_snap(a.params, a.ages, a.slots, a.slot_ages,
-                        r.snap_nodes + s0, r.snap_slots + s0, s1 - s0, a.D, s,
-                        A);
-        int r0 = r.recv_tptr[t], r1 = r.recv_tptr[t + 1];
-        if (r1 > r0) {
-            a.nodes = r.recv_nodes + r0;
-            a.ptr = r.recv_nptr + r0;
-            a.dslots = r.del_slots;
-            a.rslots = r.reply_slots;
-            L.c.dpids = d_pids;
-            mlp_comp_launch(part, L, r1 - r0, s);
-        }
-        int p0 = r.pull_tptr[t], p1 = r.pull_tptr[t + 1];
-        if (p1 > p0)
-            launch_snap(a.params, a.ages, a.slots, a.slot_ages,
-                        r.pull_nodes + p0, r.pull_slots + p0, p1 - p0, a.D, s,
-                        A);
-        int q0 = r.rep_tptr[t], q1 = r.rep_tptr[t + 1];
-        if (q1 > q0) {
-            a.nodes = r.rep_nodes + q0;
-            a.ptr = r.rep_nptr + q0;
-            a.dslots = r.rep_slots;
-            a.rslots = rep_rr;
-            L.c.dpids = r_pids;
-            mlp_comp_launch(part, L, q1 - q0, s);
-        }
-    }
+    auto L = mlp_plan(ROUND_STATE, layout, n_layers, lr, wd, epochs, bs, mode);
+    RoundArrays r = unpack_round(ROUND_EVENTS, rep_reply_slots);
+    stream_round(L, r);
 }
 
 void run_round_mlp_part(
-    torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
-    torch::Tensor slot_ages,
-    torch::Tensor snap_nodes, torch::Tensor snap_slots, torch::Tensor snap_tptr,
-    torch::Tensor recv_nodes, torch::Tensor recv_nptr, torch::Tensor recv_tptr,
-    torch::Tensor del_slots, torch::Tensor reply_slots, torch::Tensor del_pids,
-    torch::Tensor pull_nodes, torch::Tensor pull_slots, torch::Tensor pull_tptr,
-    torch::Tensor rep_nodes, torch::Tensor rep_nptr, torch::Tensor rep_tptr,
-    torch::Tensor rep_slots, torch::Tensor rep_pids,
-    torch::Tensor X, torch::Tensor Y, torch::Tensor counts,
+    ROUND_PARAMS,
     torch::Tensor layout, int64_t n_layers,
     torch::Tensor perm, torch::Tensor pptr, torch::Tensor apart,
     int64_t n_parts, double lr, double wd, int64_t epochs, int64_t bs,
     int64_t mode, torch::Tensor rep_reply_slots)
 {
-    CHECK_DEV(perm); CHECK_DEV(pptr); CHECK_DEV(apart);
-    MlpCompLaunch L = mlp_comp_setup(
-        true, params, ages, slots, slot_ages, X, Y, counts, layout, n_layers,
-        n_parts, 0, lr, wd, epochs, bs, mode);
-    TORCH_CHECK(perm.numel() == params.size(1) &&
-                apart.numel() == params.size(1) &&
-                pptr.numel() == n_parts + 1,
-                "partition tables do not match the model row");
-    L.c.perm = perm.data_ptr<int>(); L.c.pptr = pptr.data_ptr<int>();
-    L.c.apart = apart.data_ptr<int>();
-    RoundArrays r = unpack_round(snap_nodes, snap_slots, snap_tptr, recv_nodes,
-                                 recv_nptr, recv_tptr, del_slots, reply_slots,
-                                 pull_nodes, pull_slots, pull_tptr, rep_nodes,
-                                 rep_nptr, rep_tptr, rep_slots);
-    const int* d_pids = del_pids.numel() ? del_pids.data_ptr<int>() : nullptr;
-    const int* r_pids = rep_pids.numel() ? rep_pids.data_ptr<int>() : nullptr;
-    const int* rep_rr =
-        (rep_reply_slots.defined() && rep_reply_slots.numel())
-            ? rep_reply_slots.data_ptr<int>() : nullptr;
-    run_round_mlp_comp(true, L, r, d_pids, r_pids, rep_rr, (int)n_parts);
+    auto L = mlp_comp_plan(true, ROUND_STATE, layout, n_layers, perm, pptr,
+                           apart, n_parts, 0, lr, wd, epochs, bs, mode);
+    RoundArrays r = unpack_round(ROUND_EVENTS, rep_reply_slots);
+    stream_round(L, r, &MlpCompArgs::dpids);
 }
 
 void run_round_mlp_samp(
-    torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
-    torch::Tensor slot_ages,
-    torch::Tensor snap_nodes, torch::Tensor snap_slots, torch::Tensor snap_tptr,
-    torch::Tensor recv_nodes, torch::Tensor recv_nptr, torch::Tensor recv_tptr,
-    torch::Tensor del_slots, torch::Tensor reply_slots, torch::Tensor del_pids,
-    torch::Tensor pull_nodes, torch::Tensor pull_slots, torch::Tensor pull_tptr,
-    torch::Tensor rep_nodes, torch::Tensor rep_nptr, torch::Tensor rep_tptr,
-    torch::Tensor rep_slots, torch::Tensor rep_pids,
-    torch::Tensor X, torch::Tensor Y, torch::Tensor counts,
+    ROUND_PARAMS,
     torch::Tensor layout, int64_t n_layers, int64_t samp_c,
     double lr, double wd, int64_t epochs, int64_t bs, int64_t mode,
     torch::Tensor rep_reply_slots)
 {
-    MlpCompLaunch L = mlp_comp_setup(
-        false, params, ages, slots, slot_ages, X, Y, counts, layout, n_layers,
-        0, samp_c, lr, wd, epochs, bs, mode);
-    RoundArrays r = unpack_round(snap_nodes, snap_slots, snap_tptr, recv_nodes,
-                                 recv_nptr, recv_tptr, del_slots, reply_slots,
-                                 pull_nodes, pull_slots, pull_tptr, rep_nodes,
-                                 rep_nptr, rep_tptr, rep_slots);
-    const int* d_pids = del_pids.numel() ? del_pids.data_ptr<int>() : nullptr;
-    const int* r_pids = rep_pids.numel() ? rep_pids.data_ptr<int>() : nullptr;
-    const int* rep_rr =
-        (rep_reply_slots.defined() && rep_reply_slots.numel())
-            ? rep_reply_slots.data_ptr<int>() : nullptr;
-    run_round_mlp_comp(false, L, r, d_pids, r_pids, rep_rr, 1);
+    auto L = mlp_comp_plan(false, ROUND_STATE, layout, n_layers, {}, {}, {},
+                           0, samp_c, lr, wd, epochs, bs, mode);
+    RoundArrays r = unpack_round(ROUND_EVENTS, rep_reply_slots);
+    stream_round(L, r, &MlpCompArgs::dpids);
 }
+
+void run_round_mf(
+    ROUND_PARAMS,
+    int64_t k, int64_t n_items, double reg, double lr,
+    torch::Tensor rep_reply_slots)
+{
+    auto L = mf_plan(ROUND_STATE, k, n_items, reg, lr);
+    RoundArrays r = unpack_round(ROUND_EVENTS, rep_reply_slots);
+    stream_round(L, r);
+}
+
+void run_round_coop_logreg(
+    ROUND_PARAMS,
+    int64_t d, int64_t k, double lr, double wd, int64_t epochs, int64_t bs,
+    int64_t mode, int64_t max_batch)
+{
+    // NOTE: unlike the stream executor, ALL arrays (tick ptrs included)
+    // must be device-resident here.
+    CHECK_DEV(snap_tptr); CHECK_DEV(recv_tptr); CHECK_DEV(pull_tptr);
+    CHECK_DEV(rep_tptr);
+    auto L = logreg_plan(ROUND_STATE, d, k, lr, wd, epochs, bs, mode);
+    RoundArrays r = unpack_round(ROUND_EVENTS, torch::Tensor());
+    CoopRoundArgs c = round_args<CoopRoundArgs>(
+        L.a, r, r.snap_tptr, r.recv_tptr, r.pull_tptr, r.rep_tptr);
+    int grid = std::max<int>(1, (int)max_batch);
+    // stay within guaranteed cooperative residency
+    int max_blocks = 0;
+    hipError_t oerr = hipOccupancyMaxActiveBlocksPerMultiprocessor(
+        &max_blocks, (const void*)coop_round_logreg_kernel, L.threads, L.smem);
+    TORCH_CHECK(oerr == hipSuccess, "occupancy query failed");
+    hipDeviceProp_t prop;
+    (void)hipGetDeviceProperties(&prop, 0);
+    int limit = max_blocks * prop.multiProcessorCount;
+    TORCH_CHECK(limit > 0, "cooperative launch not supported");
+    if (grid > limit) grid = limit;
+    void* kargs[] = {&c};
+    hipError_t err = hipLaunchCooperativeKernel(
+        (const void*)coop_round_logreg_kernel, dim3(grid), dim3(L.threads),
+        kargs, L.smem, current_stream());
+    TORCH_CHECK(err == hipSuccess, "cooperative launch failed: ",
+                hipGetErrorString(err));
+}
+
+// ---------------------------------------------------------------------------
+// PENS and the evaluation kernels
+// ---------------------------------------------------------------------------
 
 void tick_pens(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
                torch::Tensor slot_ages, torch::Tensor nodes, torch::Tensor ptr,
@@ -3242,218 +3072,6 @@ torch::Tensor eval_metrics_scores(torch::Tensor scores, torch::Tensor Y,
     hipLaunchKernelGGL(eval_metrics_kernel, dim3(R), dim3(256), smem,
                        current_stream(), a);
     return out;
-}
-
-void run_round_logreg_samp(
-    torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
-    torch::Tensor slot_ages,
-    torch::Tensor snap_nodes, torch::Tensor snap_slots, torch::Tensor snap_tptr,
-    torch::Tensor recv_nodes, torch::Tensor recv_nptr, torch::Tensor recv_tptr,
-    torch::Tensor del_slots, torch::Tensor reply_slots, torch::Tensor del_pids,
-    torch::Tensor pull_nodes, torch::Tensor pull_slots, torch::Tensor pull_tptr,
-    torch::Tensor rep_nodes, torch::Tensor rep_nptr, torch::Tensor rep_tptr,
-    torch::Tensor rep_slots, torch::Tensor rep_pids,
-    torch::Tensor X, torch::Tensor Y, torch::Tensor counts,
-    int64_t samp_c, int64_t d, int64_t k, double lr, double wd,
-    int64_t epochs, int64_t bs, int64_t mode,
-    torch::Tensor rep_reply_slots)
-{
-    CHECK_DEV(params); CHECK_DEV(slots); CHECK_DEV(X);
-    TORCH_CHECK(mode != MODE_PASS, "Mode PASS not allowed for sampled models.");
-    RoundArrays r = unpack_round(snap_nodes, snap_slots, snap_tptr, recv_nodes,
-                                 recv_nptr, recv_tptr, del_slots, reply_slots,
-                                 pull_nodes, pull_slots, pull_tptr, rep_nodes,
-                                 rep_nptr, rep_tptr, rep_slots);
-    const int* d_pids = del_pids.numel() ? del_pids.data_ptr<int>() : nullptr;
-    const int* r_pids = rep_pids.numel() ? rep_pids.data_ptr<int>() : nullptr;
-    const int* rep_rr =
-        (rep_reply_slots.defined() && rep_reply_slots.numel())
-            ? rep_reply_slots.data_ptr<int>() : nullptr;
-    hipStream_t s = current_stream();
-    LogregSampArgs a;
-    a.params = params.data_ptr<float>(); a.ages = ages.data_ptr<int>();
-    a.slots = slots.data_ptr<float>(); a.slot_ages = slot_ages.data_ptr<int>();
-    a.X = X.data_ptr<float>(); a.Y = Y.data_ptr<float>();
-    a.counts = counts.data_ptr<int>();
-    a.samp_c = samp_c; a.d = d; a.k = k; a.Smax = X.size(1);
-    a.D = params.size(1);
-    a.lr = lr; a.wd = wd; a.epochs = epochs; a.bs = bs; a.mode = mode;
-    a.update_only = 0;
-    int bsmax = (bs == 0) ? a.Smax : std::min<int>(bs, a.Smax);
-    size_t smem = sizeof(float) * (3 * a.D + (size_t)bsmax * a.d +
-                                   (size_t)bsmax * a.k);
-    TORCH_CHECK(smem <= 160 * 1024, "sampled logreg LDS budget exceeded");
-    for (int t = 0; t < r.delta; ++t) {
-        int s0 = r.snap_tptr[t], s1 = r.snap_tptr[t + 1];
-        if (s1 > s0)
-            launch_snap(a.params, a.ages, a.slots, a.slot_ages,
-                        r.snap_nodes + s0, r.snap_slots + s0, s1 - s0, a.D, s);
-        int r0 = r.recv_tptr[t], r1 = r.recv_tptr[t + 1];
-        if (r1 > r0) {
-            a.nodes = r.recv_nodes + r0;
-            a.ptr = r.recv_nptr + r0;
-            a.dslots = r.del_slots;
-            a.rslots = r.reply_slots;
-            a.dseeds = d_pids;
-            hipLaunchKernelGGL(tick_logreg_samp_kernel, dim3(r1 - r0),
-                               dim3(128), smem, s, a);
-        }
-        int p0 = r.pull_tptr[t], p1 = r.pull_tptr[t + 1];
-        if (p1 > p0)
-            launch_snap(a.params, a.ages, a.slots, a.slot_ages,
-                        r.pull_nodes + p0, r.pull_slots + p0, p1 - p0, a.D, s);
-        int q0 = r.rep_tptr[t], q1 = r.rep_tptr[t + 1];
-        if (q1 > q0) {
-            a.nodes = r.rep_nodes + q0;
-            a.ptr = r.rep_nptr + q0;
-            a.dslots = r.rep_slots;
-            a.rslots = rep_rr;
-            a.dseeds = r_pids;
-            hipLaunchKernelGGL(tick_logreg_samp_kernel, dim3(q1 - q0),
-                               dim3(128), smem, s, a);
-        }
-    }
-}
-
-void run_round_mf(
-    torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
-    torch::Tensor slot_ages,
-    torch::Tensor snap_nodes, torch::Tensor snap_slots, torch::Tensor snap_tptr,
-    torch::Tensor recv_nodes, torch::Tensor recv_nptr, torch::Tensor recv_tptr,
-    torch::Tensor del_slots, torch::Tensor reply_slots,
-    torch::Tensor pull_nodes, torch::Tensor pull_slots, torch::Tensor pull_tptr,
-    torch::Tensor rep_nodes, torch::Tensor rep_nptr, torch::Tensor rep_tptr,
-    torch::Tensor rep_slots,
-    torch::Tensor X, torch::Tensor Y, torch::Tensor counts,
-    int64_t k, int64_t n_items, double reg, double lr,
-    torch::Tensor rep_reply_slots)
-{
-    CHECK_DEV(params); CHECK_DEV(slots); CHECK_DEV(X);
-    RoundArrays r = unpack_round(snap_nodes, snap_slots, snap_tptr, recv_nodes,
-                                 recv_nptr, recv_tptr, del_slots, reply_slots,
-                                 pull_nodes, pull_slots, pull_tptr, rep_nodes,
-                                 rep_nptr, rep_tptr, rep_slots);
-    const int* rep_rr =
-        (rep_reply_slots.defined() && rep_reply_slots.numel())
-            ? rep_reply_slots.data_ptr<int>() : nullptr;
-    hipStream_t s = current_stream();
-    MFArgs a;
-    a.params = params.data_ptr<float>(); a.ages = ages.data_ptr<int>();
-    a.slots = slots.data_ptr<float>(); a.slot_ages = slot_ages.data_ptr<int>();
-    a.X = X.data_ptr<float>(); a.Y = Y.data_ptr<float>();
-    a.counts = counts.data_ptr<int>();
-    a.k = k; a.n_items = n_items; a.Smax = X.size(1); a.D = params.size(1);
-    a.item_off = k + 1; a.Wslot = n_items * (k + 1);
-    a.reg = reg; a.lr = lr; a.update_only = 0;
-    // MF snapshots carry only the item block (src_off = item_off)
-    for (int t = 0; t < r.delta; ++t) {
-        int s0 = r.snap_tptr[t], s1 = r.snap_tptr[t + 1];
-        if (s1 > s0) {
-            long total = (long)(s1 - s0) * a.Wslot;
-            int grid = (int)std::min<long>((total + 255) / 256, 2048);
-            hipLaunchKernelGGL(snapshot_kernel, dim3(grid), dim3(256), 0, s,
-                               a.params, a.ages, a.slots,
-                               slot_ages.data_ptr<int>(), r.snap_nodes + s0,
-                               r.snap_slots + s0, s1 - s0, a.Wslot, a.D,
-                               a.item_off, 1);
-        }
-        int r0 = r.recv_tptr[t], r1 = r.recv_tptr[t + 1];
-        if (r1 > r0) {
-            a.nodes = r.recv_nodes + r0;
-            a.ptr = r.recv_nptr + r0;
-            a.dslots = r.del_slots;
-            a.rslots = r.reply_slots;
-            hipLaunchKernelGGL(tick_mf_kernel, dim3(r1 - r0), dim3(256), 0,
-                               s, a);
-        }
-        int p0 = r.pull_tptr[t], p1 = r.pull_tptr[t + 1];
-        if (p1 > p0) {
-            long total = (long)(p1 - p0) * a.Wslot;
-            int grid = (int)std::min<long>((total + 255) / 256, 2048);
-            hipLaunchKernelGGL(snapshot_kernel, dim3(grid), dim3(256), 0, s,
-                               a.params, a.ages, a.slots,
-                               slot_ages.data_ptr<int>(), r.pull_nodes + p0,
-                               r.pull_slots + p0, p1 - p0, a.Wslot, a.D,
-                               a.item_off, 1);
-        }
-        int q0 = r.rep_tptr[t], q1 = r.rep_tptr[t + 1];
-        if (q1 > q0) {
-            a.nodes = r.rep_nodes + q0;
-            a.ptr = r.rep_nptr + q0;
-            a.dslots = r.rep_slots;
-            a.rslots = rep_rr;
-            hipLaunchKernelGGL(tick_mf_kernel, dim3(q1 - q0), dim3(256), 0,
-                               s, a);
-        }
-    }
-}
-
-
-
-void run_round_coop_logreg(
-    torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
-    torch::Tensor slot_ages,
-    torch::Tensor snap_nodes, torch::Tensor snap_slots, torch::Tensor snap_tptr,
-    torch::Tensor recv_nodes, torch::Tensor recv_nptr, torch::Tensor recv_tptr,
-    torch::Tensor del_slots, torch::Tensor reply_slots,
-    torch::Tensor pull_nodes, torch::Tensor pull_slots, torch::Tensor pull_tptr,
-    torch::Tensor rep_nodes, torch::Tensor rep_nptr, torch::Tensor rep_tptr,
-    torch::Tensor rep_slots,
-    torch::Tensor X, torch::Tensor Y, torch::Tensor counts,
-    int64_t d, int64_t k, double lr, double wd, int64_t epochs, int64_t bs,
-    int64_t mode, int64_t max_batch)
-{
-    // NOTE: unlike the stream executor, ALL arrays (tick ptrs included)
-    // must be device-resident here.
-    CHECK_DEV(params); CHECK_DEV(slots); CHECK_DEV(X);
-    CHECK_DEV(snap_tptr); CHECK_DEV(recv_tptr); CHECK_DEV(pull_tptr);
-    CHECK_DEV(rep_tptr);
-    CoopRoundArgs c;
-    LogregArgs& a = c.base;
-    a.params = params.data_ptr<float>(); a.ages = ages.data_ptr<int>();
-    a.slots = slots.data_ptr<float>(); a.slot_ages = slot_ages.data_ptr<int>();
-    a.X = X.data_ptr<float>(); a.Y = Y.data_ptr<float>();
-    a.counts = counts.data_ptr<int>();
-    a.dmodes = nullptr;
-    a.d = d; a.k = k; a.Smax = X.size(1); a.D = params.size(1);
-    a.lr = lr; a.wd = wd; a.epochs = epochs; a.bs = bs; a.mode = mode;
-    a.update_only = 0;
-    auto dp = [](torch::Tensor& t) {
-        return t.numel() ? t.data_ptr<int>() : nullptr;
-    };
-    c.snap_nodes = dp(snap_nodes); c.snap_slots = dp(snap_slots);
-    c.snap_tptr = snap_tptr.data_ptr<int>();
-    c.recv_nodes = dp(recv_nodes); c.recv_nptr = recv_nptr.data_ptr<int>();
-    c.recv_tptr = recv_tptr.data_ptr<int>();
-    c.del_slots = dp(del_slots); c.reply_slots = dp(reply_slots);
-    c.pull_nodes = dp(pull_nodes); c.pull_slots = dp(pull_slots);
-    c.pull_tptr = pull_tptr.data_ptr<int>();
-    c.rep_nodes = dp(rep_nodes); c.rep_nptr = rep_nptr.data_ptr<int>();
-    c.rep_tptr = rep_tptr.data_ptr<int>();
-    c.rep_slots = dp(rep_slots);
-    c.delta = (int)snap_tptr.numel() - 1;
-
-    int bsmax = (bs == 0) ? a.Smax : std::min<int>(bs, a.Smax);
-    size_t smem = sizeof(float) * (2 * a.D + (size_t)bsmax * a.d +
-                                   (size_t)bsmax * a.k);
-    TORCH_CHECK(smem <= 160 * 1024, "logreg LDS budget exceeded");
-    int grid = std::max<int>(1, (int)max_batch);
-    // stay within guaranteed cooperative residency
-    int max_blocks = 0;
-    hipError_t oerr = hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &max_blocks, (const void*)coop_round_logreg_kernel, 128, smem);
-    TORCH_CHECK(oerr == hipSuccess, "occupancy query failed");
-    hipDeviceProp_t prop;
-    (void)hipGetDeviceProperties(&prop, 0);
-    int limit = max_blocks * prop.multiProcessorCount;
-    TORCH_CHECK(limit > 0, "cooperative launch not supported");
-    if (grid > limit) grid = limit;
-    void* kargs[] = {&c};
-    hipError_t err = hipLaunchCooperativeKernel(
-        (const void*)coop_round_logreg_kernel, dim3(grid), dim3(128), kargs,
-        smem, current_stream());
-    TORCH_CHECK(err == hipSuccess, "cooperative launch failed: ",
-                hipGetErrorString(err));
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)

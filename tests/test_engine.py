@@ -2172,6 +2172,84 @@ def _merge_invariants(f, m):
         assert len(set(ws.tolist())) == len(ws), "slot written twice in group"
 
 
+class TestFamilyCall:
+    """HIPBackend._family_call is the one spec -> extension-arguments map:
+    every family/variant the whole-round executor admits must name a tick
+    and a round op the built extension has. Nothing is launched (no GPU)."""
+
+    @staticmethod
+    def _admitted(hip, spec):
+        from types import SimpleNamespace
+
+        sim = SimpleNamespace(world=1, backend=hip, spec=spec)
+        return BatchedGossipSimulator._flat_exec_ok(sim)
+
+    def test_ops_exist_for_every_admitted_variant(self):
+        from gossipy_amd.engine import (
+            AdaLineSpec, HIPBackend, KMeansSpec, MFSpec, MLPSpec,
+        )
+
+        hip = HIPBackend()
+        round_specs = {
+            "logreg": LogRegSpec(d_in=5, n_classes=3),
+            "logreg_part": LogRegSpec(d_in=5, n_classes=3, n_parts=2),
+            "logreg_samp": LogRegSpec(d_in=5, n_classes=3, sample_size=0.3),
+            "mlp": MLPSpec(5, 3, hidden=(4,)),
+            "mlp_part": MLPSpec(5, 3, hidden=(4,), n_parts=2),
+            "mlp_samp": MLPSpec(5, 3, hidden=(4,), sample_size=0.3),
+            "linear": PegasosSpec(d_in=5),
+            "mf": MFSpec(k=4, n_items=6),
+        }
+        names = set()
+        for want, spec in round_specs.items():
+            assert self._admitted(hip, spec), want
+            name, args, chan = hip._family_call(spec, CPU)
+            assert name == want
+            assert callable(getattr(hip.ext, "tick_" + name))
+            assert callable(getattr(hip.ext, "run_round_" + name))
+            assert chan == (
+                "pids" if name.endswith(("_part", "_samp"))
+                else None if name == "mf" else "dmodes"
+            )
+            names.add(name)
+        name, _, chan = hip._family_call(AdaLineSpec(d_in=5), CPU)
+        assert (name, chan) == ("linear", "dmodes")
+        # every stream round executor of the extension is reachable
+        assert {
+            n[len("run_round_"):] for n in dir(hip.ext)
+            if n.startswith("run_round_")
+        } == names | {"coop_logreg"}
+        # tick-only family
+        km = KMeansSpec(k=3, dim=5)
+        assert not self._admitted(hip, km)
+        name, args, chan = hip._family_call(km, CPU)
+        assert (name, chan) == ("kmeans", None)
+        assert callable(hip.ext.tick_kmeans)
+
+    def test_unsupported_combinations_raise(self):
+        from types import SimpleNamespace
+
+        from gossipy_amd.engine import HIPBackend, MFSpec
+
+        hip = HIPBackend()
+        mode = CreateModelMode.MERGE_UPDATE
+        part_peg = SimpleNamespace(family="pegasos", n_parts=4, mode=mode)
+        samp_peg = SimpleNamespace(
+            family="adaline", n_parts=0, sample_size=0.3, mode=mode
+        )
+        part_mf = MFSpec(k=4, n_items=6)
+        part_mf.n_parts = 2
+        unknown = SimpleNamespace(family="torchmod", n_parts=0, mode=mode)
+        with pytest.raises(ValueError, match="partitioned gossip has no HIP path"):
+            hip._family_call(part_peg, CPU)
+        with pytest.raises(ValueError, match="sampled gossip has no HIP path"):
+            hip._family_call(samp_peg, CPU)
+        with pytest.raises(ValueError, match="partitioned gossip has no HIP path"):
+            hip._family_call(part_mf, CPU)
+        with pytest.raises(ValueError, match="torchmod"):
+            hip._family_call(unknown, CPU)
+
+
 class TestLaunchGroupMerge:
     def _flat_for(self, protocol, delay, seed, n=60, drop=0.2):
         cfg = EngineConfig(

@@ -1130,6 +1130,110 @@ class TestSingleBlockRound:
         assert torch.equal(a.state.ages, b.state.ages)
 
 
+class TestRoundExecutorGuards:
+    """The whole-round executors refuse what their tick twins refuse, with
+    the same message. Every call gets 2-row arenas and an EMPTY round (no
+    events, every tick pointer [0, 0]) plus a one-element rep_reply_slots,
+    which rules the single-workgroup fallback out: no kernel is launched
+    whether or not the check is there."""
+
+    S = 4  # samples per shard
+
+    # family -> (params width, feature width, family args) by the size under
+    # test (n_classes, d or latent k); the last SGD argument is the mode
+    # (1 = MERGE_UPDATE)
+    @staticmethod
+    def _family(name, v):
+        i32 = dict(dtype=torch.int32, device=CUDA)
+        sgd = (0.1, 0.0, 1, 0, 1)
+        if name == "logreg":
+            return 57 * v + v, 57, (57, v, *sgd)
+        if name == "logreg_part":
+            D = 57 * v + v
+            perm = torch.arange(D, **i32)
+            pptr = torch.tensor([0, D // 2, D], **i32)
+            apart = (perm >= D // 2).to(torch.int32)
+            return D, 57, (perm, pptr, apart, 2, 57, v, *sgd)
+        if name == "logreg_samp":
+            return 57 * v + v, 57, (4, 57, v, *sgd)
+        if name == "linear":
+            return v, v, (v, 0.01, 1, 1)
+        assert name == "mf"
+        return 4 * (v + 1), 2, (v, 3, 0.1, 0.05)
+
+    def _call(self, name, v):
+        """(tick error, round error): first line of the RuntimeError each
+        entry point raised, or None."""
+        ext = HIPBackend().ext
+        D, d, args = self._family(name, v)
+        aw = 2 if name == "logreg_part" else 1
+        e = torch.zeros(0, dtype=torch.int32, device=CUDA)
+        tptr = torch.zeros(2, dtype=torch.int32)
+        params = torch.zeros(2, D, device=CUDA)
+        slots = torch.zeros(2, D, device=CUDA)
+        ages = torch.zeros(2, aw, dtype=torch.int32, device=CUDA)
+        slot_ages = torch.zeros(2, aw, dtype=torch.int32, device=CUDA)
+        arena = (
+            torch.zeros(2, self.S, d, device=CUDA),
+            torch.zeros(2, self.S, device=CUDA),
+            torch.zeros(2, dtype=torch.int32, device=CUDA),
+        )
+        state = (params, ages, slots, slot_ages)
+        errs = []
+        # the tick twin on an empty batch: checks run, nothing is launched
+        pids = (e,) if name in ("logreg_part", "logreg_samp") else ()
+        dmodes = (e,) if name in ("logreg", "linear") else ()
+        calls = (
+            lambda: getattr(ext, "tick_" + name)(
+                *state, e, e, e, e, *pids, *arena, *args, False, *dmodes
+            ),
+            lambda: getattr(ext, "run_round_" + name)(
+                *state, e, e, tptr, e, e, tptr, e, e, e, e, e, tptr, e, e,
+                tptr, e, e, *arena, *args,
+                torch.zeros(1, dtype=torch.int32, device=CUDA),
+            ),
+        )
+        for call in calls:
+            try:
+                call()
+                errs.append(None)
+            except RuntimeError as ex:
+                errs.append(str(ex).splitlines()[0])
+        torch.cuda.synchronize()
+        assert not params.any() and not slots.any()
+        return errs
+
+    @pytest.mark.parametrize(
+        "name,bad,msg",
+        [
+            ("logreg", 17, "n_classes > 16 unsupported"),
+            ("logreg_part", 17, "n_classes > 16 unsupported"),
+            ("logreg_samp", 17, "n_classes > 16 unsupported"),
+            ("linear", 1025, "d > 1024 unsupported"),
+            ("mf", 65, "MF latent dim > 64 unsupported"),
+        ],
+        ids=["logreg", "logreg_part", "logreg_samp", "linear", "mf"],
+    )
+    def test_out_of_range_rejected(self, name, bad, msg):
+        tick_err, round_err = self._call(name, bad)
+        assert round_err is not None, "round executor accepted the input"
+        assert msg in round_err
+        assert round_err == tick_err
+
+    @pytest.mark.parametrize(
+        "name,ok",
+        [
+            ("logreg", 2),
+            ("logreg_part", 2),
+            ("logreg_samp", 2),
+            ("linear", 57),
+            ("mf", 8),
+        ],
+    )
+    def test_in_range_accepted(self, name, ok):
+        assert self._call(name, ok) == [None, None]
+
+
 class TestObjectLayerGPU:
     """The reference-parity object layer also runs on the MI355X (its
     per-update device round-trips are the reference's own 'GPU support'
