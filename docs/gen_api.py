@@ -128,6 +128,19 @@ to one rank) and has not been run on more than one GPU.
 |---|---|---|---|---|---|
 | partitioned (`PartitionedTMH`) | `n_parts=P` | `EngineConfig(n_parts=P)` | yes | yes | `ValueError` |
 | sampled (`SamplingTMH`) | `sample_size=f` | `EngineConfig(sampled=True)` | yes | yes | `ValueError` |
+| limited merge (`LimitedMergeTMH`) | `age_diff_threshold=L` | none | yes | yes | `TorchModuleSpec`: torch only; others `ValueError` on HIP |
+
+Limited merge (Danner 2023) is no compression scheme but lives in the same
+place, the merge: with `a` the receiver's age and `b` the received model's,
+the receiver keeps its model when `a > b + L`, adopts the received one when
+`b > a + L`, and otherwise averages with weights `a/(a+b)` and `b/(a+b)`
+(`(1/2, 1/2)` when both ages are 0, where the reference divides by zero).
+`None` is the plain mean. It needs no config switch, combines with
+`pass_through` (a PASS delivery still adopts) and not with `n_parts` or
+`sample_size`; the PENS and all2all simulators refuse it. On HIP it runs in
+second instantiations of the logreg and MLP tick kernels, per tick and
+through the stream whole-round executor; the opt-in cooperative and
+single-workgroup rounds are not extended and are bypassed.
 
 `n_parts` and `sample_size` are mutually exclusive, and `MLPSpec` rejects
 either together with `pass_through=True` (`ValueError`): PASS is an error

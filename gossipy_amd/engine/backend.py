@@ -977,6 +977,7 @@ class TorchBackend:
             return
         base_mode = spec.mode
         pt = getattr(spec, "pass_through", False)
+        L = getattr(spec, "age_diff_threshold", None)
         ptr = recv_ptr.tolist()
         for i, node_t in enumerate(recv_nodes.tolist()):
             node = torch.tensor([node_t])
@@ -987,7 +988,10 @@ class TorchBackend:
                     # pass-through adoption (gossipy/node.py:386-392)
                     mode = CreateModelMode.PASS
                 if mode == CreateModelMode.MERGE_UPDATE:
-                    self._merge_mean(state, pool, node_t, slot)
+                    if L is None:
+                        self._merge_mean(state, pool, node_t, slot)
+                    else:
+                        self._merge_limited(state, pool, node_t, slot, L)
                     self.update(state, data, spec, node)
                 elif mode == CreateModelMode.UPDATE:
                     # train the RECEIVED model on local data, adopt it
@@ -997,7 +1001,11 @@ class TorchBackend:
                 elif mode == CreateModelMode.UPDATE_MERGE:
                     self.update(state, data, spec, node)
                     self._train_slot(state, pool, data, spec, node_t, slot)
-                    self._merge_mean(state, pool, node_t, slot)
+                    if L is None:
+                        self._merge_mean(state, pool, node_t, slot)
+                    else:
+                        # the rule sees the two post-training ages
+                        self._merge_limited(state, pool, node_t, slot, L)
                 elif mode == CreateModelMode.PASS:
                     self._adopt_slot(state, pool, node_t, slot)
                 else:
@@ -1035,6 +1043,7 @@ class TorchBackend:
         if os.environ.get("GOSSIPY_TORCHMOD_LOOP") == "1":
             return False
         dev = state.params.device
+        L = getattr(spec, "age_diff_threshold", None)
         ptr = recv_ptr.long()
         cnt = ptr[1:] - ptr[:-1]
         max_w = int(cnt.max()) if len(cnt) else 0
@@ -1046,7 +1055,21 @@ class TorchBackend:
             j = ptr[:-1][rows] + w
             nodes = nodes_all[rows].to(dev)
             slots = dslots[j].to(dev)
-            if mode == CreateModelMode.MERGE_UPDATE:
+            if mode == CreateModelMode.MERGE_UPDATE and L is not None:
+                # limited merge, one weight pair per row (_merge_limited)
+                a = state.ages[nodes]
+                b = pool.slot_ages[slots]
+                m1, m2 = self._limited_weights(a, b)
+                own, recv = state.params[nodes], pool.slots[slots]
+                mixed = m1[:, None] * own + m2[:, None] * recv
+                state.params[nodes] = torch.where(
+                    (a > b + L)[:, None],
+                    own,
+                    torch.where((b > a + L)[:, None], recv, mixed),
+                )
+                state.ages[nodes] = torch.maximum(a, b)
+                self.update(state, data, spec, nodes)
+            elif mode == CreateModelMode.MERGE_UPDATE:
                 state.params[nodes] = (
                     state.params[nodes] + pool.slots[slots]
                 ) * 0.5
@@ -1072,6 +1095,42 @@ class TorchBackend:
     def _merge_mean(self, state, pool, node: int, slot: int) -> None:
         state.params[node] = (state.params[node] + pool.slots[slot]) * 0.5
         state.ages[node] = max(int(state.ages[node]), int(pool.slot_ages[slot]))
+
+    @staticmethod
+    def _limited_weights(a: torch.Tensor, b: torch.Tensor):
+        """fp32 weights ``(m1, m2) = (a/(a+b), b/(a+b))`` of the limited
+        merge's averaging branch for age tensors ``a`` (receiver) and ``b``
+        (received); ``(1/2, 1/2)`` where ``a + b == 0``. Evaluated as
+        ``float(a) / float(a + b)`` in fp32, the expression the HIP kernels
+        use."""
+        s = (a + b).to(torch.float32)
+        zero = s == 0
+        s = torch.where(zero, torch.ones_like(s), s)
+        half = torch.full_like(s, 0.5)
+        m1 = torch.where(zero, half, a.to(torch.float32) / s)
+        m2 = torch.where(zero, half, b.to(torch.float32) / s)
+        return m1, m2
+
+    def _merge_limited(self, state, pool, node: int, slot: int, L: int) -> None:
+        """Limited merge (Danner 2023; LimitedMergeMixin._merge,
+        gossipy/model/handler.py:690-715): keep the own row when it is more
+        than ``L`` updates ahead, adopt the received row when that is more
+        than ``L`` ahead, else the age-weighted average. ``a + b == 0``
+        averages with (1/2, 1/2) where the reference divides by zero."""
+        a = int(state.ages[node])
+        b = int(pool.slot_ages[slot])
+        if a > b + L:
+            pass
+        elif b > a + L:
+            state.params[node] = pool.slots[slot]
+        else:
+            m1, m2 = self._limited_weights(
+                state.ages[node], pool.slot_ages[slot]
+            )
+            state.params[node] = (
+                m1 * state.params[node] + m2 * pool.slots[slot]
+            )
+        state.ages[node] = max(a, b)
 
     def _adopt_slot(self, state, pool, node: int, slot: int) -> None:
         state.params[node] = pool.slots[slot]
@@ -1713,6 +1772,12 @@ class HIPBackend(TorchBackend):
         Raises ``ValueError`` for a family/variant without HIP kernels."""
         fam = spec.family
         mode = _MODE_ID[spec.mode]
+        L = getattr(spec, "age_diff_threshold", None)
+        if L is not None and fam not in ("logreg", "mlp"):
+            raise ValueError(
+                f"limited merge (age_diff_threshold) has no HIP path for"
+                f" family {fam!r}"
+            )
         if fam in ("logreg", "mlp"):
             sgd = (
                 spec.lr,
@@ -1747,6 +1812,9 @@ class HIPBackend(TorchBackend):
                 return "mlp_samp", (*shape, spec.samp_count(), *sgd), "pids"
             return "logreg_samp", (spec.samp_count(), *shape, *sgd), "pids"
         if fam in ("logreg", "mlp"):
+            if L is not None:
+                # the extension's second overload: merge_limit after mode
+                return fam, (*shape, *sgd, int(L)), "dmodes"
             return fam, (*shape, *sgd), "dmodes"
         if fam in ("pegasos", "adaline"):
             peg = fam == "pegasos"

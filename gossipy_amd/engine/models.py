@@ -21,7 +21,7 @@ which batched kernel trains them:
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
 import numpy as np
 
@@ -54,6 +54,40 @@ def _fortran_to_arena(layers: List[Tuple[int, int, int, int]], D: int) -> np.nda
         g += fout
     assert g == D
     return perm
+
+
+def _check_limited_merge(spec) -> None:
+    """Validate ``age_diff_threshold`` against the fields it cannot be
+    combined with (the partitioned and sampled handlers have merges of
+    their own)."""
+    L = spec.age_diff_threshold
+    if L is None:
+        return
+    name = type(spec).__name__
+    if isinstance(L, bool) or not isinstance(L, (int, np.integer)):
+        raise ValueError(
+            f"{name}: age_diff_threshold must be an int or None, got {L!r}"
+        )
+    if L < 0:
+        raise ValueError(
+            f"{name}: age_diff_threshold must be >= 0 (None selects the"
+            f" plain mean merge), got age_diff_threshold={L}"
+        )
+    if L > 2**30:
+        raise ValueError(
+            f"{name}: age_diff_threshold must be <= 2**30 (ages are int32),"
+            f" got age_diff_threshold={L}"
+        )
+    if getattr(spec, "n_parts", 0) > 0:
+        raise ValueError(
+            f"{name}: age_diff_threshold cannot be combined with n_parts"
+            " (partitioned gossip has its own age-weighted merge)"
+        )
+    if getattr(spec, "sample_size", 0) > 0:
+        raise ValueError(
+            f"{name}: age_diff_threshold cannot be combined with sample_size"
+            " (sampled gossip has its own merge)"
+        )
 
 
 class _PartitionMixin:
@@ -160,8 +194,24 @@ class LogRegSpec(_PartitionMixin):
     sample_size: float = 0.0
     #: pass-through gossip (PassThroughNode): deliveries may resolve to PASS
     pass_through: bool = False
+    #: limited merge (Danner 2023; LimitedMergeMixin._merge,
+    #: gossipy/model/handler.py:690-715). ``None`` = plain mean merge. An
+    #: int ``L >= 0`` switches every merge of this spec to the three-way
+    #: rule on the receiver's age ``a`` and the received model's age ``b``:
+    #: keep the own model when ``a > b + L``, adopt the received one when
+    #: ``b > a + L``, else ``W = a/(a+b) * W + b/(a+b) * S``; the age becomes
+    #: ``max(a, b)`` in every case. Deviation: for ``a + b == 0`` the
+    #: reference divides by zero; the engine, where a node with an empty
+    #: shard really has age 0, uses weights (1/2, 1/2). Orthogonal to
+    #: ``pass_through`` (a PASS delivery still adopts); not combinable with
+    #: ``n_parts`` or ``sample_size``. Last field, so positional
+    #: construction is unchanged.
+    age_diff_threshold: Optional[int] = None
 
     family = "logreg"
+
+    def __post_init__(self):
+        _check_limited_merge(self)
 
     def samp_count(self) -> int:
         """Coordinates per sampled merge (gossipy/model/sampling.py:57)."""
@@ -203,10 +253,14 @@ class MLPSpec(_PartitionMixin):
     #: >0 = sampled gossip (see :class:`LogRegSpec`); last field so
     #: positional construction of older call sites is unchanged
     sample_size: float = 0.0
+    #: limited merge threshold ``L`` (see :class:`LogRegSpec`); ``None`` =
+    #: plain mean merge. Last field.
+    age_diff_threshold: Optional[int] = None
 
     family = "mlp"
 
     def __post_init__(self):
+        _check_limited_merge(self)
         if self.n_parts > 0 and self.sample_size > 0:
             raise ValueError(
                 "MLPSpec: n_parts and sample_size are mutually exclusive"
@@ -407,7 +461,11 @@ class TorchModuleSpec:
         local_epochs: int = 1,
         batch_size: int = 32,
         mode: CreateModelMode = CreateModelMode.MERGE_UPDATE,
+        age_diff_threshold: Optional[int] = None,
     ):
+        #: limited merge threshold (see :class:`LogRegSpec`); torch paths only
+        self.age_diff_threshold = age_diff_threshold
+        _check_limited_merge(self)
         self.module_factory = module_factory
         self.input_shape = tuple(input_shape)
         self.lr = lr

@@ -1265,6 +1265,8 @@ class BatchedGossipSimulator(SimulationEventSender):
         if (
             name == "logreg"
             and not getattr(spec, "pass_through", False)
+            # the cooperative kernel has no limited-merge instantiation
+            and getattr(spec, "age_diff_threshold", None) is None
             and getattr(self, "_coop_enabled", True)
             and os.environ.get("GOSSIPY_COOP") == "1"
         ):
@@ -1642,6 +1644,11 @@ class BatchedAll2AllGossipSimulator(BatchedGossipSimulator):
         mixing=None,
         device: Optional[torch.device] = None,
     ):
+        if getattr(spec, "age_diff_threshold", None) is not None:
+            raise ValueError(
+                "all2all engine runs the WeightedTMH k-way merge; a spec"
+                " with age_diff_threshold (limited merge) cannot be used"
+            )
         super().__init__(cfg, spec, data, device=device)
         from ..core import CreateModelMode
 
@@ -1740,6 +1747,11 @@ class BatchedPENSGossipSimulator(BatchedGossipSimulator):
         step1_rounds: int = 10,
         device: Optional[torch.device] = None,
     ):
+        if getattr(spec, "age_diff_threshold", None) is not None:
+            raise ValueError(
+                "PENS merges the top-m candidates by plain mean; a spec with"
+                " age_diff_threshold (limited merge) cannot be used"
+            )
         super().__init__(cfg, spec, data, device=device)
         from ..core import CreateModelMode
         from .schedule import PENSScheduler

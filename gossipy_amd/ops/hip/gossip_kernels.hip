@@ -25,6 +25,11 @@
 //   tick_mlp_comp_kernel  — the MLP tick under partitioned / sampled
 //                           gossip (gossipy/model/handler.py:426-525),
 //                           same SGD body, templated on the merge policy.
+//   tick_logreg_lim_kernel, tick_mlp_kernel<true>
+//                         — the logreg / MLP ticks with the limited merge
+//                           (LimitedMergeMixin._merge,
+//                           gossipy/model/handler.py:690-715) in place of
+//                           the mean; see lim_rule.
 //
 // Models are tiny (57x2 logreg ... few-hundred-wide MLPs); per-launch work
 // is launch-latency bound, so kernels are built to let ONE launch cover all
@@ -106,7 +111,50 @@ struct LogregArgs {
     int d, k, Smax, D;
     float lr, wd;
     int epochs, bs, mode, update_only;
+    int lim;  // limited-merge threshold L (LIM kernels only); last member
 };
+
+// Limited merge (Danner 2023; LimitedMergeMixin._merge,
+// gossipy/model/handler.py:690-715): with a the receiver's age and b the
+// received model's, keep the own row when a > b + L, adopt the received row
+// when b > a + L, else W = m1*W + m2*S with m1 = a/(a+b), m2 = b/(a+b) in
+// fp32 ((1/2, 1/2) when a + b == 0, where the reference divides by zero).
+// The age becomes max(a, b) in every branch. All fields are wave-uniform.
+constexpr int LIM_KEEP = 0, LIM_ADOPT = 1, LIM_MIX = 2;
+
+struct LimRule {
+    int br;
+    float m1, m2;
+};
+
+DEV_INLINE LimRule lim_rule(int a, int b, int L)
+{
+    LimRule r{LIM_MIX, 0.5f, 0.5f};
+    if (a > b + L) {
+        r.br = LIM_KEEP;
+    } else if (b > a + L) {
+        r.br = LIM_ADOPT;
+    } else if (a + b != 0) {
+        float s = (float)(a + b);
+        r.m1 = (float)a / s;
+        r.m2 = (float)b / s;
+    }
+    return r;
+}
+
+// W[e] <- rule(W[e], S[e]) over a block-strided row; S is read only when
+// the rule needs it
+DEV_INLINE void lim_merge_row(const LimRule& r, float* W, const float* S,
+                              int D)
+{
+    if (r.br == LIM_KEEP) return;
+    if (r.br == LIM_ADOPT) {
+        for (int e = threadIdx.x; e < D; e += blockDim.x) W[e] = S[e];
+    } else {
+        for (int e = threadIdx.x; e < D; e += blockDim.x)
+            W[e] = r.m1 * W[e] + r.m2 * S[e];
+    }
+}
 
 // Minibatch SGD epochs over the node's shard, on the LDS-resident model W.
 // xb/dz are LDS scratch; age is a wave-uniform register.
@@ -184,6 +232,10 @@ DEV_INLINE void logreg_update(const LogregArgs& a, int node, float* W,
     }
 }
 
+// LIM = limited merge: every mean merge below becomes lim_rule on the two
+// ages at that point. The plain instantiation compiles to the mean-merge
+// code unchanged.
+template <bool LIM>
 DEV_INLINE void logreg_process_node(const LogregArgs& a, int i)
 {
     int node = a.nodes[i];
@@ -205,8 +257,22 @@ DEV_INLINE void logreg_process_node(const LogregArgs& a, int i)
         !(a.dmodes && a.dmodes[j0])) {
         int slot = a.dslots[j0];
         const float* srow = a.slots + (long)slot * a.D;
-        for (int e = tid; e < a.D; e += blockDim.x)
-            W[e] = 0.5f * (a.params[(long)node * a.D + e] + srow[e]);
+        if constexpr (LIM) {
+            // both ages are needed before the fused load, not after it
+            LimRule r0 = lim_rule(a.ages[node], a.slot_ages[slot], a.lim);
+            const float* prow = a.params + (long)node * a.D;
+            if (r0.br == LIM_KEEP) {
+                for (int e = tid; e < a.D; e += blockDim.x) W[e] = prow[e];
+            } else if (r0.br == LIM_ADOPT) {
+                for (int e = tid; e < a.D; e += blockDim.x) W[e] = srow[e];
+            } else {
+                for (int e = tid; e < a.D; e += blockDim.x)
+                    W[e] = r0.m1 * prow[e] + r0.m2 * srow[e];
+            }
+        } else {
+            for (int e = tid; e < a.D; e += blockDim.x)
+                W[e] = 0.5f * (a.params[(long)node * a.D + e] + srow[e]);
+        }
         int c = a.counts[node];
         int m0 = min((a.bs == 0) ? max(c, 1) : a.bs, c);
         for (int e = tid; e < m0 * a.d; e += blockDim.x)
@@ -247,12 +313,33 @@ DEV_INLINE void logreg_process_node(const LogregArgs& a, int i)
             const float* srow2 = a.slots + (long)slot2 * a.D;
             int md = (a.dmodes && a.dmodes[j]) ? MODE_PASS : a.mode;
             if (md == MODE_MERGE_UPDATE) {
-                for (int u = 0; u < PRE; ++u) {
-                    int e = tid + u * (int)blockDim.x;
-                    if (e < a.D) W[e] = 0.5f * (W[e] + pre[u]);
+                if constexpr (LIM) {
+                    // pre[] and pre_age were issued before the previous
+                    // delivery's SGD; the weights need the age AFTER it
+                    LimRule r = lim_rule(age, pre_age, a.lim);
+                    if (r.br == LIM_ADOPT) {
+                        for (int u = 0; u < PRE; ++u) {
+                            int e = tid + u * (int)blockDim.x;
+                            if (e < a.D) W[e] = pre[u];
+                        }
+                        for (int e = npre + tid; e < a.D; e += blockDim.x)
+                            W[e] = srow2[e];
+                    } else if (r.br == LIM_MIX) {
+                        for (int u = 0; u < PRE; ++u) {
+                            int e = tid + u * (int)blockDim.x;
+                            if (e < a.D) W[e] = r.m1 * W[e] + r.m2 * pre[u];
+                        }
+                        for (int e = npre + tid; e < a.D; e += blockDim.x)
+                            W[e] = r.m1 * W[e] + r.m2 * srow2[e];
+                    }
+                } else {
+                    for (int u = 0; u < PRE; ++u) {
+                        int e = tid + u * (int)blockDim.x;
+                        if (e < a.D) W[e] = 0.5f * (W[e] + pre[u]);
+                    }
+                    for (int e = npre + tid; e < a.D; e += blockDim.x)
+                        W[e] = 0.5f * (W[e] + srow2[e]);
                 }
-                for (int e = npre + tid; e < a.D; e += blockDim.x)
-                    W[e] = 0.5f * (W[e] + srow2[e]);
                 age = max(age, pre_age);
                 __syncthreads();
                 issue_pre(j + 1);
@@ -294,8 +381,12 @@ DEV_INLINE void logreg_process_node(const LogregArgs& a, int i)
             // (gossipy/node.py:380-392)
             int md = (a.dmodes && a.dmodes[j]) ? MODE_PASS : a.mode;
             if (md == MODE_MERGE_UPDATE) {
-                for (int e = tid; e < a.D; e += blockDim.x)
-                    W[e] = 0.5f * (W[e] + srow[e]);
+                if constexpr (LIM) {
+                    lim_merge_row(lim_rule(age, sage, a.lim), W, srow, a.D);
+                } else {
+                    for (int e = tid; e < a.D; e += blockDim.x)
+                        W[e] = 0.5f * (W[e] + srow[e]);
+                }
                 age = max(age, sage);
                 __syncthreads();
                 logreg_update(a, node, W, xb, dz, age);
@@ -311,8 +402,13 @@ DEV_INLINE void logreg_process_node(const LogregArgs& a, int i)
                 __syncthreads();
                 int age2 = sage;
                 logreg_update(a, node, W2, xb, dz, age2);
-                for (int e = tid; e < a.D; e += blockDim.x)
-                    W[e] = 0.5f * (W[e] + W2[e]);
+                if constexpr (LIM) {
+                    // the rule sees the two post-training ages
+                    lim_merge_row(lim_rule(age, age2, a.lim), W, W2, a.D);
+                } else {
+                    for (int e = tid; e < a.D; e += blockDim.x)
+                        W[e] = 0.5f * (W[e] + W2[e]);
+                }
                 age = max(age, age2);
                 __syncthreads();
             } else {  // PASS
@@ -340,7 +436,13 @@ DEV_INLINE void logreg_process_node(const LogregArgs& a, int i)
 __global__ void __launch_bounds__(128)
 tick_logreg_kernel(LogregArgs a)
 {
-    logreg_process_node(a, blockIdx.x);
+    logreg_process_node<false>(a, blockIdx.x);
+}
+
+__global__ void __launch_bounds__(128)
+tick_logreg_lim_kernel(LogregArgs a)
+{
+    logreg_process_node<true>(a, blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------
@@ -1092,6 +1194,7 @@ struct MlpArgs {
     int n_layers, Smax, D, act_max, d_in;
     float lr, wd;
     int epochs, bs, mode, update_only;
+    int lim;  // limited-merge threshold L (LIM kernel only); last member
 };
 
 // Fused fwd+bwd+SGD over the node's shard. LDS holds the model row plus
@@ -1354,6 +1457,8 @@ DEV_INLINE void mlp_update(const MlpArgs& a, int node, float* W,
     }
 }
 
+// LIM = limited merge (lim_rule) in place of the mean merge
+template <bool LIM>
 __global__ void __launch_bounds__(512)
 tick_mlp_kernel(MlpArgs a)
 {
@@ -1390,8 +1495,12 @@ tick_mlp_kernel(MlpArgs a)
             int sage = a.slot_ages[slot];
             int md = (a.dmodes && a.dmodes[j]) ? MODE_PASS : a.mode;
             if (md == MODE_MERGE_UPDATE) {
-                for (int e = tid; e < a.D; e += blockDim.x)
-                    W[e] = 0.5f * (W[e] + srow[e]);
+                if constexpr (LIM) {
+                    lim_merge_row(lim_rule(age, sage, a.lim), W, srow, a.D);
+                } else {
+                    for (int e = tid; e < a.D; e += blockDim.x)
+                        W[e] = 0.5f * (W[e] + srow[e]);
+                }
                 age = max(age, sage);
                 __syncthreads();
                 mlp_update<false>(a, node, W, act, grad, age);
@@ -1406,8 +1515,12 @@ tick_mlp_kernel(MlpArgs a)
                 __syncthreads();
                 int age2 = sage;
                 mlp_update<false>(a, node, W2, act, grad, age2);
-                for (int e = tid; e < a.D; e += blockDim.x)
-                    W[e] = 0.5f * (W[e] + W2[e]);
+                if constexpr (LIM) {
+                    lim_merge_row(lim_rule(age, age2, a.lim), W, W2, a.D);
+                } else {
+                    for (int e = tid; e < a.D; e += blockDim.x)
+                        W[e] = 0.5f * (W[e] + W2[e]);
+                }
                 age = max(age, age2);
                 __syncthreads();
             } else {
@@ -1965,7 +2078,7 @@ coop_round_logreg_kernel(CoopRoundArgs c)
             a.dslots = c.del_slots;
             a.rslots = c.reply_slots;
             for (int i = r0 + bid; i < r1; i += nb) {
-                logreg_process_node(a, i);
+                logreg_process_node<false>(a, i);
                 __syncthreads();
             }
             dirty = true;
@@ -1989,7 +2102,7 @@ coop_round_logreg_kernel(CoopRoundArgs c)
             a.dslots = c.rep_slots;
             a.rslots = nullptr;
             for (int i = q0 + bid; i < q1; i += nb) {
-                logreg_process_node(a, i);
+                logreg_process_node<false>(a, i);
                 __syncthreads();
             }
             dirty = true;
@@ -2264,6 +2377,16 @@ static int batch_rows(int64_t bs, int Smax)
     return (bs == 0) ? Smax : std::min<int>(bs, Smax);
 }
 
+// merge_limit of a plan: -1 = plain mean merge, L >= 0 = limited merge.
+// Ages are int32 and the rule adds L to one, so L is kept far below 2^31.
+static int check_merge_limit(int64_t merge_limit)
+{
+    TORCH_CHECK(merge_limit >= -1 && merge_limit <= (1 << 30),
+                "merge_limit must be -1 (off) or in [0, 2^30], got ",
+                merge_limit);
+    return (int)std::max<int64_t>(merge_limit, 0);
+}
+
 // the event fields live in the args struct itself, except that the
 // compressed MLP wraps a plain MlpArgs
 template <typename A> static A& events(A& a) { return a; }
@@ -2271,7 +2394,7 @@ static MlpArgs& events(MlpCompArgs& c) { return c.m; }
 
 static Plan<LogregArgs> logreg_plan(
     const StateTensors& st, int64_t d, int64_t k, double lr, double wd,
-    int64_t epochs, int64_t bs, int64_t mode)
+    int64_t epochs, int64_t bs, int64_t mode, int64_t merge_limit = -1)
 {
     Plan<LogregArgs> L;
     LogregArgs& a = L.a;
@@ -2279,10 +2402,11 @@ static Plan<LogregArgs> logreg_plan(
     TORCH_CHECK(k <= KMAX, "n_classes > ", KMAX, " unsupported");
     a.d = d; a.k = k; a.D = st.params.size(1);
     fill_sgd(a, lr, wd, epochs, bs, mode);
+    a.lim = check_merge_limit(merge_limit);
     int bsmax = batch_rows(bs, a.Smax);
     L.smem = sizeof(float) * (2 * a.D + (size_t)bsmax * a.d + (size_t)bsmax * a.k);
     TORCH_CHECK(L.smem <= 160 * 1024, "logreg LDS budget exceeded: ", L.smem);
-    L.kernel = tick_logreg_kernel;
+    L.kernel = (merge_limit >= 0) ? tick_logreg_lim_kernel : tick_logreg_kernel;
     L.threads = 128;
     L.snap = {a.D, a.D, 0, 1};
     return L;
@@ -2442,18 +2566,21 @@ static MlpGeom mlp_fill(MlpArgs& a, const StateTensors& st,
 
 static Plan<MlpArgs> mlp_plan(
     const StateTensors& st, torch::Tensor layout, int64_t n_layers, double lr,
-    double wd, int64_t epochs, int64_t bs, int64_t mode)
+    double wd, int64_t epochs, int64_t bs, int64_t mode,
+    int64_t merge_limit = -1)
 {
     Plan<MlpArgs> L;
     MlpArgs& a = L.a;
     MlpGeom g = mlp_fill(a, st, layout, n_layers, lr, wd, epochs, bs, mode);
+    a.lim = check_merge_limit(merge_limit);
     // LDS: model (+ scratch copy W2, UPDATE_MERGE only) + activations +
     // 2 grad buffers
     size_t w_slabs = (mode == MODE_UPDATE_MERGE) ? 2 : 1;
     L.smem = sizeof(float) * (w_slabs * (size_t)a.D + g.scratch);
     TORCH_CHECK(L.smem <= 160 * 1024,
         "mlp LDS budget exceeded (", L.smem, " B); shrink batch_size/hidden");
-    L.kernel = tick_mlp_kernel;
+    L.kernel = (merge_limit >= 0) ? tick_mlp_kernel<true>
+                                  : tick_mlp_kernel<false>;
     L.threads = g.threads;
     L.snap = {a.D, a.D, 0, 1};
     return L;
@@ -2535,6 +2662,23 @@ static void launch_tick(Plan<Args>& L, const TickEvents& ev, bool update_only,
     launch_kernel(L.kernel, n, L.threads, L.smem, current_stream(), L.a);
 }
 
+// The logreg and MLP entry points exist twice under one Python name: the
+// plain argument list, and one with `merge_limit` (the limited-merge
+// threshold L, -1 = off) directly after `mode`.
+void tick_logreg_lim(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
+                     torch::Tensor slot_ages, torch::Tensor nodes, torch::Tensor recv_ptr,
+                     torch::Tensor del_slots, torch::Tensor reply_slots,
+                     torch::Tensor X, torch::Tensor Y, torch::Tensor counts,
+                     int64_t d, int64_t k, double lr, double wd, int64_t epochs,
+                     int64_t bs, int64_t mode, int64_t merge_limit,
+                     bool update_only, torch::Tensor dmodes)
+{
+    auto L = logreg_plan({params, ages, slots, slot_ages, X, Y, counts},
+                         d, k, lr, wd, epochs, bs, mode, merge_limit);
+    launch_tick(L, {nodes, recv_ptr, del_slots, reply_slots}, update_only,
+                &LogregArgs::dmodes, dmodes);
+}
+
 void tick_logreg(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
                  torch::Tensor slot_ages, torch::Tensor nodes, torch::Tensor recv_ptr,
                  torch::Tensor del_slots, torch::Tensor reply_slots,
@@ -2543,10 +2687,9 @@ void tick_logreg(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
                  int64_t bs, int64_t mode, bool update_only,
                  torch::Tensor dmodes)
 {
-    auto L = logreg_plan({params, ages, slots, slot_ages, X, Y, counts},
-                         d, k, lr, wd, epochs, bs, mode);
-    launch_tick(L, {nodes, recv_ptr, del_slots, reply_slots}, update_only,
-                &LogregArgs::dmodes, dmodes);
+    tick_logreg_lim(params, ages, slots, slot_ages, nodes, recv_ptr, del_slots,
+                    reply_slots, X, Y, counts, d, k, lr, wd, epochs, bs, mode,
+                    -1, update_only, dmodes);
 }
 
 void tick_linear(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
@@ -2562,6 +2705,20 @@ void tick_linear(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
                 &LinearArgs::dmodes, dmodes);
 }
 
+void tick_mlp_lim(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
+                  torch::Tensor slot_ages, torch::Tensor nodes, torch::Tensor recv_ptr,
+                  torch::Tensor del_slots, torch::Tensor reply_slots,
+                  torch::Tensor X, torch::Tensor Y, torch::Tensor counts,
+                  torch::Tensor layout, int64_t n_layers, double lr, double wd,
+                  int64_t epochs, int64_t bs, int64_t mode, int64_t merge_limit,
+                  bool update_only, torch::Tensor dmodes)
+{
+    auto L = mlp_plan({params, ages, slots, slot_ages, X, Y, counts},
+                      layout, n_layers, lr, wd, epochs, bs, mode, merge_limit);
+    launch_tick(L, {nodes, recv_ptr, del_slots, reply_slots}, update_only,
+                &MlpArgs::dmodes, dmodes);
+}
+
 void tick_mlp(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
               torch::Tensor slot_ages, torch::Tensor nodes, torch::Tensor recv_ptr,
               torch::Tensor del_slots, torch::Tensor reply_slots,
@@ -2570,10 +2727,9 @@ void tick_mlp(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
               int64_t epochs, int64_t bs, int64_t mode, bool update_only,
               torch::Tensor dmodes)
 {
-    auto L = mlp_plan({params, ages, slots, slot_ages, X, Y, counts},
-                      layout, n_layers, lr, wd, epochs, bs, mode);
-    launch_tick(L, {nodes, recv_ptr, del_slots, reply_slots}, update_only,
-                &MlpArgs::dmodes, dmodes);
+    tick_mlp_lim(params, ages, slots, slot_ages, nodes, recv_ptr, del_slots,
+                 reply_slots, X, Y, counts, layout, n_layers, lr, wd, epochs,
+                 bs, mode, -1, update_only, dmodes);
 }
 
 void tick_logreg_part(
@@ -2846,16 +3002,29 @@ static bool single_block_round(void (*kernel)(RoundArgs), const Plan<Args>& L,
     return true;
 }
 
+void run_round_logreg_lim(
+    ROUND_PARAMS,
+    int64_t d, int64_t k, double lr, double wd, int64_t epochs, int64_t bs,
+    int64_t mode, int64_t merge_limit, torch::Tensor rep_reply_slots)
+{
+    auto L = logreg_plan(ROUND_STATE, d, k, lr, wd, epochs, bs, mode,
+                         merge_limit);
+    RoundArrays r = unpack_round(ROUND_EVENTS, rep_reply_slots);
+    // the single-workgroup round kernel has no limited-merge instantiation
+    if (merge_limit < 0 &&
+        single_block_round(coop_round_logreg_kernel, L, r, params.device()))
+        return;
+    stream_round(L, r);
+}
+
 void run_round_logreg(
     ROUND_PARAMS,
     int64_t d, int64_t k, double lr, double wd, int64_t epochs, int64_t bs,
     int64_t mode, torch::Tensor rep_reply_slots)
 {
-    auto L = logreg_plan(ROUND_STATE, d, k, lr, wd, epochs, bs, mode);
-    RoundArrays r = unpack_round(ROUND_EVENTS, rep_reply_slots);
-    if (single_block_round(coop_round_logreg_kernel, L, r, params.device()))
-        return;
-    stream_round(L, r);
+    run_round_logreg_lim(params, ages, slots, slot_ages, ROUND_EVENTS, X, Y,
+                         counts, d, k, lr, wd, epochs, bs, mode, -1,
+                         rep_reply_slots);
 }
 
 void run_round_linear(
@@ -2895,14 +3064,26 @@ void run_round_logreg_samp(
     stream_round(L, r, &LogregSampArgs::dseeds);
 }
 
+void run_round_mlp_lim(
+    ROUND_PARAMS,
+    torch::Tensor layout, int64_t n_layers, double lr, double wd,
+    int64_t epochs, int64_t bs, int64_t mode, int64_t merge_limit,
+    torch::Tensor rep_reply_slots)
+{
+    auto L = mlp_plan(ROUND_STATE, layout, n_layers, lr, wd, epochs, bs, mode,
+                      merge_limit);
+    RoundArrays r = unpack_round(ROUND_EVENTS, rep_reply_slots);
+    stream_round(L, r);
+}
+
 void run_round_mlp(
     ROUND_PARAMS,
     torch::Tensor layout, int64_t n_layers, double lr, double wd,
     int64_t epochs, int64_t bs, int64_t mode, torch::Tensor rep_reply_slots)
 {
-    auto L = mlp_plan(ROUND_STATE, layout, n_layers, lr, wd, epochs, bs, mode);
-    RoundArrays r = unpack_round(ROUND_EVENTS, rep_reply_slots);
-    stream_round(L, r);
+    run_round_mlp_lim(params, ages, slots, slot_ages, ROUND_EVENTS, X, Y,
+                      counts, layout, n_layers, lr, wd, epochs, bs, mode, -1,
+                      rep_reply_slots);
 }
 
 void run_round_mlp_part(
@@ -3078,10 +3259,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
 {
     m.def("snapshot", &snapshot, "batched model snapshot (arena row copy)");
     m.def("tick_logreg", &tick_logreg, "fused merge + logreg SGD tick");
+    m.def("tick_logreg", &tick_logreg_lim,
+          "fused merge + logreg SGD tick, merge_limit after mode");
     m.def("tick_linear", &tick_linear, "fused merge + pegasos/adaline tick");
     m.def("tick_mlp", &tick_mlp, "fused merge + MLP SGD tick");
+    m.def("tick_mlp", &tick_mlp_lim,
+          "fused merge + MLP SGD tick, merge_limit after mode");
     m.def("run_round_logreg", &run_round_logreg,
           "whole-round executor, logreg family",
+          py::call_guard<py::gil_scoped_release>());
+    m.def("run_round_logreg", &run_round_logreg_lim,
+          "whole-round executor, logreg family, merge_limit after mode",
           py::call_guard<py::gil_scoped_release>());
     m.def("run_round_linear", &run_round_linear,
           "whole-round executor, pegasos/adaline family",
@@ -3098,6 +3286,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           "fused item-block merge + per-rating MF SGD tick (K9/K10)");
     m.def("run_round_mlp", &run_round_mlp,
           "whole-round executor, MLP family",
+          py::call_guard<py::gil_scoped_release>());
+    m.def("run_round_mlp", &run_round_mlp_lim,
+          "whole-round executor, MLP family, merge_limit after mode",
           py::call_guard<py::gil_scoped_release>());
     m.def("tick_mlp_part", &tick_mlp_part,
           "fused partition-merge + age-rescaled MLP SGD tick");
