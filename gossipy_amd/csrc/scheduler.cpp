@@ -24,6 +24,7 @@
 #include <cmath>
 #include <cstdint>
 #include <map>
+#include <memory>
 #include <deque>
 #include <functional>
 #include <unordered_map>
@@ -31,6 +32,8 @@
 #include <cstdio>
 #include <unordered_set>
 #include <vector>
+
+#include "round_prefetch.h"
 
 namespace py = pybind11;
 
@@ -203,7 +206,18 @@ static std::vector<int32_t> compute_merge_bounds(
 // chains no longer fragment the round. Returns packed arrays in the
 // executors' format.
 // ---------------------------------------------------------------------------
-static py::dict pack_round(
+// the packed arrays, in plain C++ (no Python objects: a worker thread may
+// compute them without the GIL); emit_packed turns them into the dict
+struct PackedRound {
+    std::vector<int32_t> snap_nodes, snap_slots, snap_tptr{0};
+    std::vector<int32_t> recv_nodes, recv_nptr{0}, recv_tptr{0};
+    std::vector<int32_t> del_slots, reply_slots, del_pids, del_owners;
+    std::vector<int32_t> rep_nodes, rep_nptr{0}, rep_tptr{0};
+    std::vector<int32_t> rep_slots, rep_reply_slots, rep_pids, rep_owners;
+    std::vector<int32_t> pull_tptr{};
+};
+
+static PackedRound pack_round_compute(
     const std::vector<int32_t>& snap_nodes, const std::vector<int32_t>& snap_slots,
     const std::vector<int32_t>& snap_tptr,
     const std::vector<int32_t>& recv_nodes, const std::vector<int32_t>& recv_nptr,
@@ -225,14 +239,8 @@ static py::dict pack_round(
 
     struct Ev { int32_t slot, reply, pid, own, next; };
     struct Row { int32_t node, head, tail; };
-    struct Out {
-        std::vector<int32_t> snap_nodes, snap_slots, snap_tptr{0};
-        std::vector<int32_t> recv_nodes, recv_nptr{0}, recv_tptr{0};
-        std::vector<int32_t> del_slots, reply_slots, del_pids, del_owners;
-        std::vector<int32_t> rep_nodes, rep_nptr{0}, rep_tptr{0};
-        std::vector<int32_t> rep_slots, rep_reply_slots, rep_pids, rep_owners;
-        std::vector<int32_t> pull_tptr{};
-    } o;
+    using Out = PackedRound;
+    Out o;
     o.snap_nodes.reserve(snap_nodes.size() + pull_nodes.size());
     o.snap_slots.reserve(snap_slots.size() + pull_slots.size());
     o.recv_nodes.reserve(recv_nodes.size());
@@ -481,6 +489,11 @@ static py::dict pack_round(
 
     int32_t n_groups = (int32_t)o.snap_tptr.size() - 1;
     o.pull_tptr.assign((size_t)n_groups + 1, 0);
+    return o;
+}
+
+static py::dict emit_packed(PackedRound& o)
+{
     py::dict pd;
     auto arr = [](std::vector<int32_t>& v) {
         auto a = py::array_t<int32_t>((py::ssize_t)v.size());
@@ -510,6 +523,47 @@ static py::dict pack_round(
     pd["rep_owners"] = arr(o.rep_owners);
     return pd;
 }
+
+static py::dict pack_round(
+    const std::vector<int32_t>& snap_nodes, const std::vector<int32_t>& snap_slots,
+    const std::vector<int32_t>& snap_tptr,
+    const std::vector<int32_t>& recv_nodes, const std::vector<int32_t>& recv_nptr,
+    const std::vector<int32_t>& recv_tptr,
+    const std::vector<int32_t>& del_slots, const std::vector<int32_t>& reply_slots,
+    const std::vector<int32_t>& del_pids,
+    const std::vector<int32_t>& pull_nodes, const std::vector<int32_t>& pull_slots,
+    const std::vector<int32_t>& pull_tptr,
+    const std::vector<int32_t>& rep_nodes, const std::vector<int32_t>& rep_nptr,
+    const std::vector<int32_t>& rep_tptr, const std::vector<int32_t>& rep_slots,
+    const std::vector<int32_t>& rep_pids,
+    const std::vector<int32_t>& del_owners,
+    const std::vector<int32_t>& rep_owners,
+    int64_t n_nodes, int64_t n_slots)
+{
+    PackedRound o = pack_round_compute(
+        snap_nodes, snap_slots, snap_tptr, recv_nodes, recv_nptr, recv_tptr,
+        del_slots, reply_slots, del_pids, pull_nodes, pull_slots, pull_tptr,
+        rep_nodes, rep_nptr, rep_tptr, rep_slots, rep_pids, del_owners,
+        rep_owners, n_nodes, n_slots);
+    return emit_packed(o);
+}
+
+// One round of the plain scheduler as plain C++ data: the full per-event
+// vectors, the packed arrays, the counters and the eval draw. A worker
+// thread may fill it; NativeScheduler::emit_round converts it on the
+// calling thread.
+struct RoundData {
+    std::vector<int32_t> snap_nodes, snap_slots, snap_tptr{0};
+    std::vector<int32_t> recv_nodes, recv_tptr{0};
+    std::vector<int32_t> recv_nptr{0};
+    std::vector<int32_t> del_slots, del_owners, reply_slots, del_pids;
+    std::vector<int32_t> pull_nodes, pull_slots, pull_tptr{0};
+    std::vector<int32_t> rep_nodes, rep_tptr{0}, rep_nptr{0};
+    std::vector<int32_t> rep_slots, rep_owners, rep_pids;
+    PackedRound packed;
+    int64_t sent = 0, failed = 0, total_size = 0, n_slots = 0;
+    std::vector<int64_t> eval_nodes;  // empty: no evaluation this round
+};
 
 class NativeScheduler {
 public:
@@ -551,9 +605,44 @@ public:
         }
     }
 
+    // the prefetch worker runs compute_round on this object: stop it
+    // before any member goes away
+    ~NativeScheduler() { prefetch_.reset(); }
+
     py::dict next_round(int64_t r);
 
+    // Generate rounds on a C++ worker thread, up to two ahead of the one
+    // last asked for; next_round(r) then only waits (GIL released) and
+    // converts. Rounds must be asked for in order while this is on. Off
+    // (the default) is the synchronous path; turning it off keeps the
+    // rounds already generated and serves them first.
+    void set_prefetch(bool on)
+    {
+        if (on == (prefetch_ != nullptr)) return;
+        if (on) {
+            if (!ahead_.empty())
+                throw std::invalid_argument(
+                    "set_prefetch(True) with prefetched rounds pending");
+            prefetch_ = std::make_unique<RoundPrefetch<RoundData>>(
+                [this](int64_t r) { return compute_round(r); }, next_r_);
+        } else {
+            std::vector<RoundData> rest;
+            {
+                py::gil_scoped_release nogil;
+                rest = prefetch_->drain();
+            }
+            prefetch_.reset();
+            for (auto& d : rest) ahead_.push_back(std::move(d));
+        }
+    }
+
 protected:
+    RoundData compute_round(int64_t r);
+    py::dict emit_round(RoundData& d);
+    std::unique_ptr<RoundPrefetch<RoundData>> prefetch_;
+    std::deque<RoundData> ahead_;  // generated by a worker since stopped
+    int64_t next_r_ = 0;           // round after the last one handed out
+
     int64_t n_, delta_;
     int proto_;
     int64_t model_size_;
@@ -728,16 +817,55 @@ protected:
 py::dict NativeScheduler::next_round(int64_t r)
 {
     auto t_start0 = std::chrono::steady_clock::now();
-    const int64_t t0 = r * delta_, t1 = (r + 1) * delta_;
-    int64_t sent = 0, failed = 0, total_size = 0;
+    RoundData d;
+    if (prefetch_) {
+        if (r != next_r_)
+            throw std::invalid_argument(
+                "rounds are prefetched in order: expected round " +
+                std::to_string(next_r_) + ", got " + std::to_string(r));
+        py::gil_scoped_release nogil;
+        d = prefetch_->take(r);
+    } else if (!ahead_.empty()) {
+        if (r != next_r_)
+            throw std::invalid_argument(
+                "prefetched rounds pending: expected round " +
+                std::to_string(next_r_) + ", got " + std::to_string(r));
+        d = std::move(ahead_.front());
+        ahead_.pop_front();
+    } else {
+        d = compute_round(r);
+    }
+    next_r_ = r + 1;
+    auto t_mid0 = std::chrono::steady_clock::now();
+    py::dict out = emit_round(d);
+    if (getenv("GOSSIPY_SCHED_TIME")) {
+        static double t_loop = 0, t_emit = 0;
+        auto t_end0 = std::chrono::steady_clock::now();
+        t_loop += std::chrono::duration<double>(t_mid0 - t_start0).count();
+        t_emit += std::chrono::duration<double>(t_end0 - t_mid0).count();
+        fprintf(stderr, "[sched] loop=%.3fms emit=%.3fms (cum)\n",
+                t_loop * 1000, t_emit * 1000);
+    }
+    return out;
+}
 
-    std::vector<int32_t> snap_nodes, snap_slots, snap_tptr{0};
-    std::vector<int32_t> recv_nodes, recv_tptr{0};
-    std::vector<int32_t> recv_nptr{0};
-    std::vector<int32_t> del_slots, del_owners, reply_slots, del_pids;
-    std::vector<int32_t> pull_nodes, pull_slots, pull_tptr{0};
-    std::vector<int32_t> rep_nodes, rep_tptr{0}, rep_nptr{0};
-    std::vector<int32_t> rep_slots, rep_owners, rep_pids;
+RoundData NativeScheduler::compute_round(int64_t r)
+{
+    const int64_t t0 = r * delta_, t1 = (r + 1) * delta_;
+    RoundData rd;
+    int64_t &sent = rd.sent, &failed = rd.failed, &total_size = rd.total_size;
+    auto &snap_nodes = rd.snap_nodes, &snap_slots = rd.snap_slots,
+         &snap_tptr = rd.snap_tptr;
+    auto &recv_nodes = rd.recv_nodes, &recv_tptr = rd.recv_tptr,
+         &recv_nptr = rd.recv_nptr;
+    auto &del_slots = rd.del_slots, &del_owners = rd.del_owners,
+         &reply_slots = rd.reply_slots, &del_pids = rd.del_pids;
+    auto &pull_nodes = rd.pull_nodes, &pull_slots = rd.pull_slots,
+         &pull_tptr = rd.pull_tptr;
+    auto &rep_nodes = rd.rep_nodes, &rep_tptr = rd.rep_tptr,
+         &rep_nptr = rd.rep_nptr;
+    auto &rep_slots = rd.rep_slots, &rep_owners = rd.rep_owners,
+         &rep_pids = rd.rep_pids;
 
     std::vector<double> online(n_);
     std::vector<int32_t> firing;
@@ -929,71 +1057,73 @@ py::dict NativeScheduler::next_round(int64_t r)
         for (int32_t s : freed) reuse_q_.emplace_back(t, s);
     }
 
-    auto t_mid0 = std::chrono::steady_clock::now();
+    rd.n_slots = next_slot_;
+    rd.packed = pack_round_compute(
+        snap_nodes, snap_slots, snap_tptr, recv_nodes, recv_nptr,
+        recv_tptr, del_slots, reply_slots, del_pids, pull_nodes,
+        pull_slots, pull_tptr, rep_nodes, rep_nptr, rep_tptr, rep_slots,
+        rep_pids, del_owners, rep_owners, n_, next_slot_);
+    if (sampling_eval_ > 0) {
+        Stream g(stream_key(seed_, EVAL, (uint64_t)(t1 - 1), 0));
+        int64_t k = std::max<int64_t>((int64_t)(n_ * sampling_eval_), 1);
+        rd.eval_nodes.resize(k);
+        for (int64_t i = 0; i < k; ++i) rd.eval_nodes[i] = g.integers(0, n_);
+    }
+    return rd;
+}
+
+// lean_ is read here, at emit time, so set_lean never races with rounds a
+// worker generated ahead
+py::dict NativeScheduler::emit_round(RoundData& d)
+{
     py::dict out;
     auto arr = [](std::vector<int32_t>& v) {
         auto a = py::array_t<int32_t>((py::ssize_t)v.size());
         std::copy(v.begin(), v.end(), a.mutable_data());
         return a;
     };
-    out["snap_tptr"] = arr(snap_tptr);
-    out["recv_tptr"] = arr(recv_tptr);
-    out["pull_tptr"] = arr(pull_tptr);
-    out["rep_tptr"] = arr(rep_tptr);
+    out["snap_tptr"] = arr(d.snap_tptr);
+    out["recv_tptr"] = arr(d.recv_tptr);
+    out["pull_tptr"] = arr(d.pull_tptr);
+    out["rep_tptr"] = arr(d.rep_tptr);
     if (!lean_) {
-        out["snap_nodes"] = arr(snap_nodes);
-        out["snap_slots"] = arr(snap_slots);
-        out["recv_nodes"] = arr(recv_nodes);
-        out["recv_nptr"] = arr(recv_nptr);
-        out["del_slots"] = arr(del_slots);
-        out["del_owners"] = arr(del_owners);
-        out["reply_slots"] = arr(reply_slots);
-        out["pull_nodes"] = arr(pull_nodes);
-        out["pull_slots"] = arr(pull_slots);
-        out["rep_nodes"] = arr(rep_nodes);
-        out["rep_nptr"] = arr(rep_nptr);
-        out["rep_slots"] = arr(rep_slots);
-        out["rep_owners"] = arr(rep_owners);
-        out["del_pids"] = arr(del_pids);
-        out["rep_pids"] = arr(rep_pids);
+        out["snap_nodes"] = arr(d.snap_nodes);
+        out["snap_slots"] = arr(d.snap_slots);
+        out["recv_nodes"] = arr(d.recv_nodes);
+        out["recv_nptr"] = arr(d.recv_nptr);
+        out["del_slots"] = arr(d.del_slots);
+        out["del_owners"] = arr(d.del_owners);
+        out["reply_slots"] = arr(d.reply_slots);
+        out["pull_nodes"] = arr(d.pull_nodes);
+        out["pull_slots"] = arr(d.pull_slots);
+        out["rep_nodes"] = arr(d.rep_nodes);
+        out["rep_nptr"] = arr(d.rep_nptr);
+        out["rep_slots"] = arr(d.rep_slots);
+        out["rep_owners"] = arr(d.rep_owners);
+        out["del_pids"] = arr(d.del_pids);
+        out["rep_pids"] = arr(d.rep_pids);
     }
 
-    out["sent"] = sent;
-    out["failed"] = failed;
-    out["total_size"] = total_size;
-    out["n_slots"] = next_slot_;
-    {
-        if (!lean_) {
-            auto mb = compute_merge_bounds(
-                n_, next_slot_, snap_nodes, snap_slots, snap_tptr, recv_nodes,
-                recv_nptr, recv_tptr, del_slots, reply_slots, pull_nodes,
-                pull_slots, pull_tptr, rep_nodes, rep_nptr, rep_tptr,
-                rep_slots);
-            out["merge_bounds"] = arr(mb);
-        }
-        out["packed"] = pack_round(
-            snap_nodes, snap_slots, snap_tptr, recv_nodes, recv_nptr,
-            recv_tptr, del_slots, reply_slots, del_pids, pull_nodes,
-            pull_slots, pull_tptr, rep_nodes, rep_nptr, rep_tptr, rep_slots,
-            rep_pids, del_owners, rep_owners, n_, next_slot_);
+    out["sent"] = d.sent;
+    out["failed"] = d.failed;
+    out["total_size"] = d.total_size;
+    out["n_slots"] = d.n_slots;
+    if (!lean_) {
+        auto mb = compute_merge_bounds(
+            n_, d.n_slots, d.snap_nodes, d.snap_slots, d.snap_tptr,
+            d.recv_nodes, d.recv_nptr, d.recv_tptr, d.del_slots,
+            d.reply_slots, d.pull_nodes, d.pull_slots, d.pull_tptr,
+            d.rep_nodes, d.rep_nptr, d.rep_tptr, d.rep_slots);
+        out["merge_bounds"] = arr(mb);
     }
-    if (sampling_eval_ > 0) {
-        Stream g(stream_key(seed_, EVAL, (uint64_t)(t1 - 1), 0));
-        int64_t k = std::max<int64_t>((int64_t)(n_ * sampling_eval_), 1);
-        auto ev = py::array_t<int64_t>(k);
-        for (int64_t i = 0; i < k; ++i)
-            ev.mutable_data()[i] = g.integers(0, n_);
+    out["packed"] = emit_packed(d.packed);
+    if (!d.eval_nodes.empty()) {
+        auto ev = py::array_t<int64_t>((py::ssize_t)d.eval_nodes.size());
+        std::copy(d.eval_nodes.begin(), d.eval_nodes.end(),
+                  ev.mutable_data());
         out["eval_nodes"] = ev;
     } else {
         out["eval_nodes"] = py::none();
-    }
-    if (getenv("GOSSIPY_SCHED_TIME")) {
-        static double t_loop = 0, t_emit = 0;
-        auto t_end0 = std::chrono::steady_clock::now();
-        t_loop += std::chrono::duration<double>(t_mid0 - t_start0).count();
-        t_emit += std::chrono::duration<double>(t_end0 - t_mid0).count();
-        fprintf(stderr, "[sched] loop=%.3fms emit=%.3fms (cum)\n",
-                t_loop * 1000, t_emit * 1000);
     }
     return out;
 }
@@ -1474,7 +1604,8 @@ PYBIND11_MODULE(_gossip_sched, m)
              py::arg("peers_indptr"), py::arg("peers_indices"),
              py::arg("n_parts") = 0, py::arg("sampled") = false)
         .def("next_round", &NativeScheduler::next_round)
-        .def("set_lean", &NativeScheduler::set_lean);
+        .def("set_lean", &NativeScheduler::set_lean)
+        .def("set_prefetch", &NativeScheduler::set_prefetch);
     py::class_<NativeTokenizedScheduler>(m, "NativeTokenizedScheduler")
         .def(py::init<int64_t, int64_t, int, int64_t, double, double, int,
                       int64_t, int64_t, double, int64_t, bool, double,

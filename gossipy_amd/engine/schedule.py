@@ -1676,3 +1676,13 @@ def _adapter_set_lean(self, v: bool) -> None:
 
 
 NativeSchedulerAdapter.set_lean = _adapter_set_lean
+
+
+def _adapter_set_prefetch(self, v: bool) -> None:
+    """Generate rounds on the native scheduler's own worker thread, up to
+    two ahead; ``next_round*`` then only waits and converts, and rounds must
+    be asked for in order. Pure C++ on the worker: no GIL hand-offs."""
+    self._native.set_prefetch(v)
+
+
+NativeSchedulerAdapter.set_prefetch = _adapter_set_prefetch

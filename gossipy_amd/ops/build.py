@@ -25,7 +25,8 @@ def build_sched(verbose: bool = False) -> str:
         name="_gossip_sched",
         sources=[src],
         build_directory=build_dir,
-        extra_cflags=["-O3"],
+        extra_cflags=["-O3", "-pthread"],
+        extra_ldflags=["-pthread"],
         verbose=verbose,
         is_python_module=False,
         with_cuda=False,
@@ -54,7 +55,7 @@ def build_sched_asan(verbose: bool = False) -> str:
     # ASAN-linked .so refuses without the runtime preloaded
     cmd = [
         "g++", "-O1", "-g", "-std=c++17", "-shared", "-fPIC",
-        "-fsanitize=address", "-fno-omit-frame-pointer",
+        "-fsanitize=address", "-fno-omit-frame-pointer", "-pthread",
         # PYBIND11_MODULE(_gossip_sched, m) -> rename the token so the
         # PyInit_ symbol matches this .so's filename
         "-D_gossip_sched=_gossip_sched_asan",

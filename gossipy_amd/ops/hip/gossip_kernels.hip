@@ -156,14 +156,142 @@ DEV_INLINE void lim_merge_row(const LimRule& r, float* W, const float* S,
     }
 }
 
+// Latency-chain helpers. A workgroup here is a handful of waves working on
+// one tiny model, so every loop below is bound by memory round trips, not
+// by throughput: a read that is waited for before the next one is issued
+// costs a full LDS (or HBM) latency per element. Each helper therefore
+// issues a fixed block of CH reads into registers before the first use.
+constexpr int CH = 8;
+
+// dst[e] = src[e], e < n, block-strided; all of a thread's loads of a
+// chunk are in flight before its first store (any address spaces)
+template <int U = CH>
+DEV_INLINE void copy_row(float* dst, const float* src, int n)
+{
+    int tid = threadIdx.x, bd = blockDim.x;
+    for (int base = tid; base < n; base += U * bd) {
+        float v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            int e = base + u * bd;
+            v[u] = (e < n) ? src[e] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            int e = base + u * bd;
+            if (e < n) dst[e] = v[u];
+        }
+    }
+}
+
+// W[e] = f(W[e], S[e]), e < D, block-strided, S reads batched
+template <typename F>
+DEV_INLINE void merge_rows(float* W, const float* S, int D, F f)
+{
+    int tid = threadIdx.x, bd = blockDim.x;
+    for (int base = tid; base < D; base += CH * bd) {
+        float v[CH];
+#pragma unroll
+        for (int u = 0; u < CH; ++u) {
+            int e = base + u * bd;
+            v[u] = (e < D) ? S[e] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < CH; ++u) {
+            int e = base + u * bd;
+            if (e < D) W[e] = f(W[e], v[u]);
+        }
+    }
+}
+
+// W[e] = f(P[e], S[e]) for e < D and xb[e] = X[e] for e < nx in one pass:
+// the three HBM streams of a chunk are in flight before the first LDS write
+template <typename F>
+DEV_INLINE void fused_stage(float* W, const float* P, const float* S, int D,
+                            float* xb, const float* X, int nx, F f)
+{
+    int tid = threadIdx.x, bd = blockDim.x;
+    int n = max(D, nx);
+    for (int base = tid; base < n; base += CH * bd) {
+        float pv[CH], sv[CH], xv[CH];
+#pragma unroll
+        for (int u = 0; u < CH; ++u) {
+            int e = base + u * bd;
+            pv[u] = (e < D) ? P[e] : 0.f;
+            sv[u] = (e < D) ? S[e] : 0.f;
+            xv[u] = (e < nx) ? X[e] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < CH; ++u) {
+            int e = base + u * bd;
+            if (e < D) W[e] = f(pv[u], sv[u]);
+            if (e < nx) xb[e] = xv[u];
+        }
+    }
+}
+
+// acc + <w, x> as ONE chain of fused multiply-adds in order e = 0..d-1
+// (the arithmetic of `for e: acc += w[e] * x[e]`), with the reads of CH
+// elements issued ahead of the CH dependent FMAs
+DEV_INLINE float dot_chain(float acc, const float* w, const float* x, int d)
+{
+    int e0 = 0;
+    for (; e0 + CH <= d; e0 += CH) {
+        float wv[CH], xv[CH];
+#pragma unroll
+        for (int u = 0; u < CH; ++u) { wv[u] = w[e0 + u]; xv[u] = x[e0 + u]; }
+#pragma unroll
+        for (int u = 0; u < CH; ++u) acc = fmaf(wv[u], xv[u], acc);
+    }
+    if (e0 < d) {  // tail: clamped reads, masked FMAs
+        float wv[CH], xv[CH];
+#pragma unroll
+        for (int u = 0; u < CH; ++u) {
+            int e = min(e0 + u, d - 1);
+            wv[u] = w[e]; xv[u] = x[e];
+        }
+#pragma unroll
+        for (int u = 0; u < CH; ++u)
+            if (e0 + u < d) acc = fmaf(wv[u], xv[u], acc);
+    }
+    return acc;
+}
+
+// sum over s = 0..m-1, in that order, of p[s*ps] * q[s*qs] (q == nullptr:
+// of p[s*ps]), starting from +0; reads batched as in dot_chain. m >= 1.
+DEV_INLINE float col_chain(const float* p, int ps, const float* q, int qs,
+                           int m)
+{
+    float g = 0.f;
+    for (int s0 = 0; s0 < m; s0 += CH) {
+        float pv[CH], qv[CH];
+#pragma unroll
+        for (int u = 0; u < CH; ++u) {
+            int s = min(s0 + u, m - 1);
+            pv[u] = p[s * ps];
+            qv[u] = q ? q[s * qs] : 0.f;
+        }
+        if (q) {
+#pragma unroll
+            for (int u = 0; u < CH; ++u)
+                if (s0 + u < m) g = fmaf(pv[u], qv[u], g);
+        } else {
+#pragma unroll
+            for (int u = 0; u < CH; ++u)
+                if (s0 + u < m) g += pv[u];
+        }
+    }
+    return g;
+}
+
 // Minibatch SGD epochs over the node's shard, on the LDS-resident model W.
-// xb/dz are LDS scratch; age is a wave-uniform register.
-DEV_INLINE void logreg_update(const LogregArgs& a, int node, float* W,
+// xb/dz are LDS scratch; age is a wave-uniform register; c = counts[node],
+// read once by the caller.
+DEV_INLINE void logreg_update(const LogregArgs& a, int node, int c, float* W,
                               float* xb, float* dz, int& age,
                               int prestaged = 0)
 {
     int tid = threadIdx.x;
-    int c = a.counts[node];
     if (c == 0) return;
     int bsz = (a.bs == 0) ? c : min(a.bs, c);
     const float* Xn = a.X + (long)node * a.Smax * a.d;
@@ -174,56 +302,55 @@ DEV_INLINE void logreg_update(const LogregArgs& a, int node, float* W,
     for (int ep = 0; ep < a.epochs; ++ep) {
         for (int s0 = 0; s0 < c; s0 += bsz) {
             int m = min(bsz, c - s0);
+            // the label is consumed only in the dz stage: its HBM trip
+            // hides under the staging and the forward pass
+            float yv = (tid < m) ? Yn[s0 + tid] : 0.f;
             // stage the batch in LDS (coalesced: consecutive threads read
             // consecutive floats of the shard); the caller may have staged
             // the very first batch already (fused with the W load)
-            if (!xb_valid) {
-                for (int e = tid; e < m * a.d; e += blockDim.x)
-                    xb[e] = Xn[(long)s0 * a.d + e];
-            }
+            if (!xb_valid) copy_row(xb, Xn + (long)s0 * a.d, m * a.d);
             xb_valid = (c <= bsz);
             __syncthreads();
-            // per-sample forward + dLoss/dz (thread = sample)
+            // forward: the m*k (sample, class) scores spread over the
+            // block, parked in the dz area
+            for (int pr = tid; pr < m * a.k; pr += blockDim.x) {
+                int s = pr / a.k, kk = pr - s * a.k;
+                dz[pr] = dot_chain(W[a.k * a.d + kk],  // bias
+                                   W + kk * a.d, xb + s * a.d, a.d);
+            }
+            __syncthreads();
+            // dLoss/dz (thread = sample), in place over the sample's own k
+            // scores: a = sigmoid(z); p = softmax(a);
+            // dz = (p - 1_y)/m * a*(1-a)
             if (tid < m) {
-                float z[KMAX];
-                for (int kk = 0; kk < a.k; ++kk) {
-                    float acc = W[a.k * a.d + kk];  // bias
-                    const float* wrow = W + kk * a.d;
-                    const float* xrow = xb + tid * a.d;
-                    for (int dd = 0; dd < a.d; ++dd) acc += wrow[dd] * xrow[dd];
-                    z[kk] = acc;
-                }
-                // a = sigmoid(z); p = softmax(a); dz = (p - 1_y)/m * a*(1-a)
+                float* zs = dz + tid * a.k;
                 float amax = -1e30f;
                 for (int kk = 0; kk < a.k; ++kk) {
-                    z[kk] = 1.0f / (1.0f + __expf(-z[kk]));
-                    amax = fmaxf(amax, z[kk]);
+                    float sg = 1.0f / (1.0f + __expf(-zs[kk]));
+                    zs[kk] = sg;
+                    amax = fmaxf(amax, sg);
                 }
                 float sum = 0.f;
-                float p[KMAX];
-                for (int kk = 0; kk < a.k; ++kk) {
-                    p[kk] = __expf(z[kk] - amax);
-                    sum += p[kk];
-                }
-                int yi = (int)Yn[s0 + tid];
+                for (int kk = 0; kk < a.k; ++kk) sum += __expf(zs[kk] - amax);
+                int yi = (int)yv;
                 float inv = 1.0f / sum;
                 for (int kk = 0; kk < a.k; ++kk) {
-                    float g = p[kk] * inv - (kk == yi ? 1.0f : 0.0f);
-                    dz[tid * a.k + kk] = (g / m) * z[kk] * (1.0f - z[kk]);
+                    float sg = zs[kk];
+                    float pk = __expf(sg - amax);
+                    float g = pk * inv - (kk == yi ? 1.0f : 0.0f);
+                    zs[kk] = (g / m) * sg * (1.0f - sg);
                 }
             }
             __syncthreads();
             // SGD step (thread = parameter)
             for (int e = tid; e < a.k * a.d; e += blockDim.x) {
                 int kk = e / a.d, dd = e - kk * a.d;
-                float g = 0.f;
-                for (int s = 0; s < m; ++s) g += dz[s * a.k + kk] * xb[s * a.d + dd];
+                float g = col_chain(dz + kk, a.k, xb + dd, a.d, m);
                 if (a.wd != 0.f) g += a.wd * W[e];
                 W[e] -= a.lr * g;
             }
             for (int e = tid; e < a.k; e += blockDim.x) {
-                float g = 0.f;
-                for (int s = 0; s < m; ++s) g += dz[s * a.k + e];
+                float g = col_chain(dz + e, a.k, nullptr, 0, m);
                 W[a.k * a.d + e] -= a.lr * g;
             }
             __syncthreads();
@@ -240,6 +367,7 @@ DEV_INLINE void logreg_process_node(const LogregArgs& a, int i)
 {
     int node = a.nodes[i];
     int tid = threadIdx.x;
+    int c = a.counts[node];  // once per receiver row
     extern __shared__ float sm[];
     float* W = sm;                         // D
     float* W2 = W + a.D;                   // D (UPDATE_MERGE scratch)
@@ -257,32 +385,34 @@ DEV_INLINE void logreg_process_node(const LogregArgs& a, int i)
         !(a.dmodes && a.dmodes[j0])) {
         int slot = a.dslots[j0];
         const float* srow = a.slots + (long)slot * a.D;
+        const float* prow = a.params + (long)node * a.D;
+        const float* X0 = a.X + (long)node * a.Smax * a.d;
+        int age0 = a.ages[node], sage0 = a.slot_ages[slot];
+        int m0 = min((a.bs == 0) ? max(c, 1) : a.bs, c);
         if constexpr (LIM) {
             // both ages are needed before the fused load, not after it
-            LimRule r0 = lim_rule(a.ages[node], a.slot_ages[slot], a.lim);
-            const float* prow = a.params + (long)node * a.D;
+            LimRule r0 = lim_rule(age0, sage0, a.lim);
             if (r0.br == LIM_KEEP) {
-                for (int e = tid; e < a.D; e += blockDim.x) W[e] = prow[e];
+                fused_stage(W, prow, srow, a.D, xb, X0, m0 * a.d,
+                            [](float p, float) { return p; });
             } else if (r0.br == LIM_ADOPT) {
-                for (int e = tid; e < a.D; e += blockDim.x) W[e] = srow[e];
+                fused_stage(W, prow, srow, a.D, xb, X0, m0 * a.d,
+                            [](float, float s) { return s; });
             } else {
-                for (int e = tid; e < a.D; e += blockDim.x)
-                    W[e] = r0.m1 * prow[e] + r0.m2 * srow[e];
+                fused_stage(W, prow, srow, a.D, xb, X0, m0 * a.d,
+                            [&](float p, float s) {
+                                return r0.m1 * p + r0.m2 * s;
+                            });
             }
         } else {
-            for (int e = tid; e < a.D; e += blockDim.x)
-                W[e] = 0.5f * (a.params[(long)node * a.D + e] + srow[e]);
+            fused_stage(W, prow, srow, a.D, xb, X0, m0 * a.d,
+                        [](float p, float s) { return 0.5f * (p + s); });
         }
-        int c = a.counts[node];
-        int m0 = min((a.bs == 0) ? max(c, 1) : a.bs, c);
-        for (int e = tid; e < m0 * a.d; e += blockDim.x)
-            xb[e] = a.X[(long)node * a.Smax * a.d + e];
         __syncthreads();
-        int age = max(a.ages[node], a.slot_ages[slot]);
+        int age = max(age0, sage0);
         // xb holds batch 0 after the fused stage above; it STAYS valid for
         // later deliveries only when the shard is a single batch
-        int c0 = a.counts[node];
-        int xb_keep = (a.bs == 0) || (c0 <= a.bs);
+        int xb_keep = (a.bs == 0) || (c <= a.bs);
         // register double-buffer: issue the NEXT delivery's slot-row loads
         // before each (long) update so the HBM latency hides under compute
         constexpr int PRE = 8;
@@ -300,11 +430,10 @@ DEV_INLINE void logreg_process_node(const LogregArgs& a, int i)
             }
         };
         issue_pre(j0 + 1);
-        logreg_update(a, node, W, xb, dz, age, /*prestaged=*/1);
+        logreg_update(a, node, c, W, xb, dz, age, /*prestaged=*/1);
         int rs0 = a.rslots ? a.rslots[j0] : -1;
         if (rs0 >= 0) {  // first delivery's PUSH_PULL reply snapshot
-            for (int e = tid; e < a.D; e += blockDim.x)
-                a.slots[(long)rs0 * a.D + e] = W[e];
+            copy_row(a.slots + (long)rs0 * a.D, W, a.D);
             if (tid == 0) a.slot_ages[rs0] = age;
             __syncthreads();
         }
@@ -322,56 +451,54 @@ DEV_INLINE void logreg_process_node(const LogregArgs& a, int i)
                             int e = tid + u * (int)blockDim.x;
                             if (e < a.D) W[e] = pre[u];
                         }
-                        for (int e = npre + tid; e < a.D; e += blockDim.x)
-                            W[e] = srow2[e];
+                        copy_row(W + npre, srow2 + npre, a.D - npre);
                     } else if (r.br == LIM_MIX) {
                         for (int u = 0; u < PRE; ++u) {
                             int e = tid + u * (int)blockDim.x;
                             if (e < a.D) W[e] = r.m1 * W[e] + r.m2 * pre[u];
                         }
-                        for (int e = npre + tid; e < a.D; e += blockDim.x)
-                            W[e] = r.m1 * W[e] + r.m2 * srow2[e];
+                        merge_rows(W + npre, srow2 + npre, a.D - npre,
+                                   [&](float w, float s) {
+                                       return r.m1 * w + r.m2 * s;
+                                   });
                     }
                 } else {
                     for (int u = 0; u < PRE; ++u) {
                         int e = tid + u * (int)blockDim.x;
                         if (e < a.D) W[e] = 0.5f * (W[e] + pre[u]);
                     }
-                    for (int e = npre + tid; e < a.D; e += blockDim.x)
-                        W[e] = 0.5f * (W[e] + srow2[e]);
+                    merge_rows(W + npre, srow2 + npre, a.D - npre,
+                               [](float w, float s) { return 0.5f * (w + s); });
                 }
                 age = max(age, pre_age);
                 __syncthreads();
                 issue_pre(j + 1);
-                logreg_update(a, node, W, xb, dz, age, /*prestaged=*/xb_keep);
+                logreg_update(a, node, c, W, xb, dz, age, /*prestaged=*/xb_keep);
             } else {  // PASS (pass-through coin resolved to adopt)
-                for (int e = tid; e < a.D; e += blockDim.x) W[e] = srow2[e];
+                copy_row(W, srow2, a.D);
                 age = a.slot_ages[slot2];
                 __syncthreads();
                 issue_pre(j + 1);
             }
             int rs2 = a.rslots ? a.rslots[j] : -1;
             if (rs2 >= 0) {
-                for (int e = tid; e < a.D; e += blockDim.x)
-                    a.slots[(long)rs2 * a.D + e] = W[e];
+                copy_row(a.slots + (long)rs2 * a.D, W, a.D);
                 if (tid == 0) a.slot_ages[rs2] = age;
                 __syncthreads();
             }
         }
         __syncthreads();
-        for (int e = tid; e < a.D; e += blockDim.x)
-            a.params[(long)node * a.D + e] = W[e];
+        copy_row(a.params + (long)node * a.D, W, a.D);
         if (tid == 0) a.ages[node] = age;
         return;
     }
 
-    for (int e = tid; e < a.D; e += blockDim.x)
-        W[e] = a.params[(long)node * a.D + e];
+    copy_row(W, a.params + (long)node * a.D, a.D);
     __syncthreads();
     int age = a.ages[node];
 
     if (a.update_only) {
-        logreg_update(a, node, W, xb, dz, age);
+        logreg_update(a, node, c, W, xb, dz, age);
     } else {
         for (int j = a.ptr[i]; j < a.ptr[i + 1]; ++j) {
             int slot = a.dslots[j];
@@ -384,24 +511,25 @@ DEV_INLINE void logreg_process_node(const LogregArgs& a, int i)
                 if constexpr (LIM) {
                     lim_merge_row(lim_rule(age, sage, a.lim), W, srow, a.D);
                 } else {
-                    for (int e = tid; e < a.D; e += blockDim.x)
-                        W[e] = 0.5f * (W[e] + srow[e]);
+                    merge_rows(W, srow, a.D, [](float w, float s) {
+                        return 0.5f * (w + s);
+                    });
                 }
                 age = max(age, sage);
                 __syncthreads();
-                logreg_update(a, node, W, xb, dz, age);
+                logreg_update(a, node, c, W, xb, dz, age);
             } else if (md == MODE_UPDATE) {
                 // adopt the received model, then train it
-                for (int e = tid; e < a.D; e += blockDim.x) W[e] = srow[e];
+                copy_row(W, srow, a.D);
                 age = sage;
                 __syncthreads();
-                logreg_update(a, node, W, xb, dz, age);
+                logreg_update(a, node, c, W, xb, dz, age);
             } else if (md == MODE_UPDATE_MERGE) {
-                logreg_update(a, node, W, xb, dz, age);
-                for (int e = tid; e < a.D; e += blockDim.x) W2[e] = srow[e];
+                logreg_update(a, node, c, W, xb, dz, age);
+                copy_row(W2, srow, a.D);
                 __syncthreads();
                 int age2 = sage;
-                logreg_update(a, node, W2, xb, dz, age2);
+                logreg_update(a, node, c, W2, xb, dz, age2);
                 if constexpr (LIM) {
                     // the rule sees the two post-training ages
                     lim_merge_row(lim_rule(age, age2, a.lim), W, W2, a.D);
@@ -412,7 +540,7 @@ DEV_INLINE void logreg_process_node(const LogregArgs& a, int i)
                 age = max(age, age2);
                 __syncthreads();
             } else {  // PASS
-                for (int e = tid; e < a.D; e += blockDim.x) W[e] = srow[e];
+                copy_row(W, srow, a.D);
                 age = sage;
                 __syncthreads();
             }
@@ -420,16 +548,14 @@ DEV_INLINE void logreg_process_node(const LogregArgs& a, int i)
             // replies are discarded, gossipy/simul.py:426)
             int rs = a.rslots ? a.rslots[j] : -1;
             if (rs >= 0) {  // PUSH_PULL reply snapshot (post merge+update)
-                for (int e = tid; e < a.D; e += blockDim.x)
-                    a.slots[(long)rs * a.D + e] = W[e];
+                copy_row(a.slots + (long)rs * a.D, W, a.D);
                 if (tid == 0) a.slot_ages[rs] = age;
                 __syncthreads();
             }
         }
     }
     __syncthreads();
-    for (int e = tid; e < a.D; e += blockDim.x)
-        a.params[(long)node * a.D + e] = W[e];
+    copy_row(a.params + (long)node * a.D, W, a.D);
     if (tid == 0) a.ages[node] = age;
 }
 
@@ -752,9 +878,10 @@ tick_logreg_samp_kernel(LogregSampArgs a)
     u.X = a.X; u.Y = a.Y; u.counts = a.counts;
     u.d = a.d; u.k = a.k; u.Smax = a.Smax; u.D = a.D;
     u.lr = a.lr; u.wd = a.wd; u.epochs = a.epochs; u.bs = a.bs;
+    int cn = a.counts[node];
 
     if (a.update_only) {
-        logreg_update(u, node, W, xb, dz, age);
+        logreg_update(u, node, cn, W, xb, dz, age);
     } else {
         for (int j = a.ptr[i]; j < a.ptr[i + 1]; ++j) {
             int slot = a.dslots[j];
@@ -763,17 +890,17 @@ tick_logreg_samp_kernel(LogregSampArgs a)
             int sage = a.slot_ages[slot];
             if (a.mode == MODE_MERGE_UPDATE) {
                 logreg_samp_merge(a, W, W3, srow, seed);
-                logreg_update(u, node, W, xb, dz, age);
+                logreg_update(u, node, cn, W, xb, dz, age);
             } else {
                 // UPDATE: train received, merge its sample into self
                 // (handler.py:440-442); UPDATE_MERGE: self-update first
                 // (handler.py:445-448)
                 if (a.mode == MODE_UPDATE_MERGE)
-                    logreg_update(u, node, W, xb, dz, age);
+                    logreg_update(u, node, cn, W, xb, dz, age);
                 for (int e = tid; e < a.D; e += blockDim.x) W2[e] = srow[e];
                 __syncthreads();
                 int age2 = sage;
-                logreg_update(u, node, W2, xb, dz, age2);
+                logreg_update(u, node, cn, W2, xb, dz, age2);
                 logreg_samp_merge(a, W, W3, W2, seed);
             }
             int rs = a.rslots ? a.rslots[j] : -1;
@@ -1756,13 +1883,13 @@ eval_metrics_kernel(EvalArgs a)
     extern __shared__ float sm[];
     float* W = sm;                       // D
     float* s1 = W + a.D;                 // n_eval: positive-class score
-    char* yb = (char*)(s1 + n_e);   // n_eval: binarized label
+    float* cs = s1 + n_e;                // n_eval: s1 compacted by label
+    char* yb = (char*)(cs + n_e);   // n_eval: binarized label
     int* conf = (int*)(yb + ((n_e + 15) & ~15));  // k*k confusion
     float* XT = (float*)(conf + EVAL_KMAX * EVAL_KMAX);  // tile x d
     int kk = a.is_margin ? 2 : a.k;
 
-    for (int e = tid; e < a.D; e += blockDim.x)
-        W[e] = a.params[(long)node * a.D + e];
+    copy_row(W, a.params + (long)node * a.D, a.D);
     for (int e = tid; e < kk * kk; e += blockDim.x) conf[e] = 0;
     __syncthreads();
 
@@ -1798,68 +1925,105 @@ eval_metrics_kernel(EvalArgs a)
     // the kernel's 44 us)
     for (int s0 = 0; s0 < n_e; s0 += a.tile) {
         int m = min(a.tile, n_e - s0);
-        for (int e = tid; e < m * a.d; e += blockDim.x)
-            XT[e] = Xb[(long)s0 * a.d + e];
+        copy_row<16>(XT, Xb + (long)s0 * a.d, m * a.d);
         __syncthreads();
         for (int sidx = s0 + tid; sidx < s0 + m; sidx += blockDim.x) {
             const float* x = XT + (long)(sidx - s0) * a.d;
+            float yv = Yb[sidx];  // in flight under the scoring
             int pred, yt;
             float sc1;
             if (a.is_margin) {
-                float acc = 0.f;
-                for (int e = 0; e < a.d; ++e) acc += W[e] * x[e];
+                float acc = dot_chain(0.f, W, x, a.d);
                 sc1 = acc;
                 pred = acc >= 0.f ? 1 : 0;
-                yt = Yb[sidx] > 0.f ? 1 : 0;
+                yt = yv > 0.f ? 1 : 0;
             } else {
                 float best = -1e30f;
                 int bj = 0;
                 float z1 = 0.f;
                 for (int j = 0; j < a.k; ++j) {
-                    float acc = W[a.k * a.d + j];
-                    const float* wrow = W + j * a.d;
-                    for (int e = 0; e < a.d; ++e) acc += wrow[e] * x[e];
+                    float acc = dot_chain(W[a.k * a.d + j],  // bias
+                                          W + j * a.d, x, a.d);
                     if (acc > best) { best = acc; bj = j; }
                     if (j == 1) z1 = acc;
                 }
                 sc1 = z1;
                 pred = bj;
-                yt = (int)Yb[sidx];
+                yt = (int)yv;
             }
             s1[sidx] = sc1;
-            yb[sidx] = (char)(a.is_margin ? (Yb[sidx] > 0.f ? 1 : 0)
-                                          : ((int)Yb[sidx] == 1 ? 1 : 0));
+            yb[sidx] = (char)(a.is_margin ? (yv > 0.f ? 1 : 0)
+                                          : ((int)yv == 1 ? 1 : 0));
             atomicAdd(&conf[yt * kk + pred], 1);
         }
         __syncthreads();
     }
 
     // pairwise AUC (binary only): wins over (pos, neg) pairs, ties 0.5 —
-    // the Mann-Whitney statistic (== average-rank AUC)
+    // the Mann-Whitney statistic (== average-rank AUC). Every partial sum
+    // is a multiple of 0.5 below 2^24, so the fp32 total does not depend
+    // on the summation order.
     __shared__ float auc_wins;
-    __shared__ int npos_s;
-    if (tid == 0) { auc_wins = 0.f; npos_s = 0; }
+    __shared__ int npos_s, nneg_s;
+    if (tid == 0) { auc_wins = 0.f; npos_s = 0; nneg_s = 0; }
     __syncthreads();
     if (kk == 2) {
+        // compact the scores by label: positives fill cs from the front,
+        // negatives from the back (one LDS atomic per wave and label)
+        int lane = tid & (WAVE - 1);
+        unsigned long long below = (1ull << lane) - 1ull;
+        for (int i0 = 0; i0 < n_e; i0 += blockDim.x) {
+            int i = i0 + tid;
+            bool in = i < n_e;
+            bool ps = in && yb[in ? i : 0];
+            bool ng = in && !ps;
+            float sc = s1[in ? i : 0];
+            unsigned long long mp = __ballot(ps), mn = __ballot(ng);
+            int bp = 0, bn = 0;
+            if (lane == 0) {
+                bp = atomicAdd(&npos_s, __popcll(mp));
+                bn = atomicAdd(&nneg_s, __popcll(mn));
+            }
+            bp = __shfl(bp, 0, WAVE);
+            bn = __shfl(bn, 0, WAVE);
+            if (ps) cs[bp + __popcll(mp & below)] = sc;
+            if (ng) cs[n_e - 1 - (bn + __popcll(mn & below))] = sc;
+        }
+        __syncthreads();
+        int npos = npos_s, nneg = n_e - npos;
+        int total = npos * nneg;  // <= 2^20 for n_e <= 2048
+        const float* pos = cs;
+        const float* neg = cs + npos;
         float wins = 0.f;
-        int npos_l = 0;
-        for (int i = tid; i < n_e; i += blockDim.x) {
-            if (!yb[i]) continue;
-            npos_l += 1;
-            for (int j = 0; j < n_e; ++j) {
-                if (yb[j]) continue;
-                if (s1[i] > s1[j]) wins += 1.f;
-                else if (s1[i] == s1[j]) wins += 0.5f;
+        if (total > 0) {
+            // pair q = i*nneg + j; a thread walks q = tid, tid + B, ... and
+            // keeps (i, j) by adding (B / nneg, B % nneg) with one carry
+            int B = blockDim.x;
+            int di = B / nneg, dj = B - di * nneg;
+            int i = tid / nneg, j = tid - i * nneg;
+            for (int q0 = tid; q0 < total; q0 += CH * B) {
+                float pv[CH], nv[CH];
+                bool ok[CH];
+#pragma unroll
+                for (int u = 0; u < CH; ++u) {
+                    ok[u] = q0 + u * B < total;
+                    pv[u] = pos[min(i, npos - 1)];
+                    nv[u] = neg[j];
+                    i += di; j += dj;
+                    if (j >= nneg) { j -= nneg; i += 1; }
+                }
+#pragma unroll
+                for (int u = 0; u < CH; ++u) {
+                    float w = pv[u] > nv[u] ? 1.f
+                                            : (pv[u] == nv[u] ? 0.5f : 0.f);
+                    wins += ok[u] ? w : 0.f;
+                }
             }
         }
         // block reduce via wave shuffles: 256 serialized LDS atomics were
         // ~1/3 of this kernel's time
         wins = wave_sum(wins);
-        float np_f = wave_sum((float)npos_l);
-        if ((tid & 63) == 0) {
-            atomicAdd(&auc_wins, wins);
-            atomicAdd(&npos_s, (int)np_f);
-        }
+        if (lane == 0) atomicAdd(&auc_wins, wins);
     }
     __syncthreads();
 
@@ -2004,7 +2168,7 @@ tick_pens_kernel(PensArgs a)
     u.X = a.X; u.Y = a.Y; u.counts = a.dcounts;
     u.d = a.d; u.k = a.k; u.Smax = a.Smax; u.D = a.D;
     u.lr = a.lr; u.wd = a.wd; u.epochs = a.epochs; u.bs = a.bs;
-    logreg_update(u, node, W, xb, dz, age);
+    logreg_update(u, node, c_n, W, xb, dz, age);
     __syncthreads();
     for (int e = tid; e < a.D; e += blockDim.x)
         a.params[(long)node * a.D + e] = W[e];
@@ -3209,9 +3373,10 @@ torch::Tensor eval_metrics(torch::Tensor params, torch::Tensor nodes,
     a.is_margin = is_margin;
     a.scores = nullptr;
     a.eval_counts = per_node ? eval_counts.data_ptr<int>() : nullptr;
-    // LDS: model + scores + binarized labels + confusion + one X tile.
+    // LDS: model + scores + their label-compacted copy + binarized labels
+    // + confusion + one X tile.
     // The tile size adapts so everything fits the 160 KB budget.
-    size_t fixed = sizeof(float) * (a.D + n_eval)
+    size_t fixed = sizeof(float) * (a.D + 2 * (size_t)n_eval)
         + ((n_eval + 15) & ~15) * sizeof(char)
         + sizeof(int) * EVAL_KMAX * EVAL_KMAX;
     long room = (long)(160 * 1024 - fixed) / (long)(sizeof(float) * d);
@@ -3246,7 +3411,7 @@ torch::Tensor eval_metrics_scores(torch::Tensor scores, torch::Tensor Y,
     a.tile = 1;
     a.eval_counts = nullptr;
     a.scores = scores.data_ptr<float>();
-    size_t smem = sizeof(float) * n_eval
+    size_t smem = sizeof(float) * 2 * (size_t)n_eval
         + ((n_eval + 15) & ~15) * sizeof(char)
         + sizeof(int) * EVAL_KMAX * EVAL_KMAX;
     TORCH_CHECK(smem <= 160 * 1024, "eval LDS budget exceeded: ", smem);
