@@ -26,12 +26,51 @@ sim = BatchedGossipSimulator(cfg, spec, data, device=device)
 sim.init_nodes()
 print("fast path:", sim._fast_path_ok())
 
-T = {"sched": 0.0, "run": 0.0, "pref": 0.0, "eval": 0.0, "sync": 0.0}
 for w in range(5):
     sim.start(n_rounds=1)
 torch.cuda.synchronize()
 
 N = 20
+drv = sim._round_driver()
+if drv is not None:
+    # the native round driver (GOSSIPY_NO_ROUND_DRIVER=1 probes the Python
+    # path below instead): step = the one native call, poll = collecting
+    # finished metrics, rest = the Python bookkeeping around them
+    D = {"step": 0.0, "poll": 0.0, "rest": 0.0, "sync": 0.0}
+    s0 = drv.stats()
+    t_all0 = time.perf_counter()
+    for i in range(N):
+        r = sim.rounds_done
+        t0 = time.perf_counter()
+        res = drv.step(r)
+        assert res[4] >= 0, "pool growth inside the timed loop"
+        t1 = time.perf_counter()
+        blocks = drv.poll_eval(False)
+        t2 = time.perf_counter()
+        sim._add_message_counts(res[0], res[1], res[2])
+        sim._report_driver_evals(blocks)
+        sim.rounds_done += 1
+        sim.notify_timestep((r + 1) * cfg.delta - 1)
+        t3 = time.perf_counter()
+        torch.cuda.synchronize()
+        t4 = time.perf_counter()
+        D["step"] += t1 - t0
+        D["poll"] += t2 - t1
+        D["rest"] += t3 - t2
+        D["sync"] += t4 - t3
+    t_all1 = time.perf_counter()
+    sim._report_driver_evals(drv.drain())
+    print("round driver:")
+    for k, v in D.items():
+        print(f"{k:6s}: {v/N*1000:8.3f} ms/round")
+    print(f"total : {(t_all1-t_all0)/N*1000:8.3f} ms/round")
+    s1 = drv.stats()
+    print(f"inside step: take {(s1[0]-s0[0])/N*1000:.3f}, "
+          f"layout+enqueue {(s1[1]-s0[1])/N*1000:.3f} ms/round")
+    sys.exit(0)
+
+print("python round path:")
+T = {"sched": 0.0, "run": 0.0, "pref": 0.0, "eval": 0.0, "sync": 0.0}
 t_all0 = time.perf_counter()
 for i in range(N):
     r = sim.rounds_done

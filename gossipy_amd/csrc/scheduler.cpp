@@ -33,7 +33,9 @@
 #include <unordered_set>
 #include <vector>
 
+#include "round_layout.h"
 #include "round_prefetch.h"
+#include "round_source.h"
 
 namespace py = pybind11;
 
@@ -607,12 +609,35 @@ public:
 
     // the prefetch worker runs compute_round on this object: stop it
     // before any member goes away
-    ~NativeScheduler() { prefetch_.reset(); }
+    ~NativeScheduler()
+    {
+        prefetch_.reset();
+        gen_.reset();
+    }
 
     py::dict next_round(int64_t r);
 
-    // Generate rounds on a C++ worker thread, up to two ahead of the one
-    // last asked for; next_round(r) then only waits (GIL released) and
+    // The same rounds for a native executor, with no Python objects on the
+    // way (csrc/round_source.h): a capsule holding a RoundSource whose
+    // take(r) needs no GIL. take() and next_round() draw from one sequence
+    // and may be mixed between rounds; take() insists on r being the next
+    // round whatever the mode, and reports anything else as an error.
+    py::capsule round_source()
+    {
+        source_.self = this;
+        source_.take = &NativeScheduler::take_thunk;
+        return py::capsule(&source_, "gossipy_amd.RoundSource");
+    }
+
+    // Round r in the executors' upload layout (csrc/round_layout.h), written
+    // into a caller-supplied int32 array: what the RoundDriver uploads, for
+    // checking without a GPU. Returns (lens, tptrs, counters, eval ids);
+    // raises, without consuming the round, when buf is too small.
+    py::tuple next_round_packed_into(int64_t r, py::array_t<int32_t> buf);
+
+    // Generate rounds on C++ worker threads (one runs the tick loop, one
+    // packs what it produced, each up to two rounds ahead of its taker);
+    // next_round(r) then only waits (GIL released) and
     // converts. Rounds must be asked for in order while this is on. Off
     // (the default) is the synchronous path; turning it off keeps the
     // rounds already generated and serves them first.
@@ -623,22 +648,55 @@ public:
             if (!ahead_.empty())
                 throw std::invalid_argument(
                     "set_prefetch(True) with prefetched rounds pending");
+            gen_ = std::make_unique<RoundPrefetch<RoundData>>(
+                [this](int64_t r) { return generate_round(r); }, next_r_);
+            RoundPrefetch<RoundData>* gen = gen_.get();
+            const int64_t n = n_;
             prefetch_ = std::make_unique<RoundPrefetch<RoundData>>(
-                [this](int64_t r) { return compute_round(r); }, next_r_);
+                [gen, n](int64_t r) {
+                    RoundData d = gen->take(r);
+                    pack_generated(d, n);
+                    return d;
+                },
+                next_r_);
         } else {
-            std::vector<RoundData> rest;
+            std::vector<RoundData> rest, unpacked;
             {
                 py::gil_scoped_release nogil;
+                // the packer first (it may be waiting on the generator,
+                // which keeps producing until it is stopped in turn)
                 rest = prefetch_->drain();
+                unpacked = gen_->drain();
+                for (auto& d : unpacked) pack_generated(d, n_);
             }
             prefetch_.reset();
+            gen_.reset();
             for (auto& d : rest) ahead_.push_back(std::move(d));
+            for (auto& d : unpacked) ahead_.push_back(std::move(d));
         }
     }
 
 protected:
+    // a round = generate_round (the tick loop: all the scheduler's state)
+    // + pack_generated (launch packing: none of it)
     RoundData compute_round(int64_t r);
+    RoundData generate_round(int64_t r);
+    static void pack_generated(RoundData& rd, int64_t n_nodes);
     py::dict emit_round(RoundData& d);
+    // the next round from wherever it is waiting: rounds handed back or
+    // left by a stopped worker first, then the worker, else computed now.
+    // Does not advance next_r_. No GIL needed.
+    RoundData fetch_round(int64_t r, bool strict);
+    // take(r) of the RoundSource: fetch into held_ and describe it
+    void take_view(int64_t r, RoundView* out);
+    static int take_thunk(void* self, int64_t r, RoundView* out, char* err,
+                          size_t errlen);
+    RoundSource source_{};
+    RoundData held_;  // what the last take() handed out
+    // two workers in a pipeline: gen_ generates rounds, prefetch_ takes
+    // them from gen_ and packs them. gen_ is declared first: prefetch_'s
+    // worker uses it, so prefetch_ goes away first.
+    std::unique_ptr<RoundPrefetch<RoundData>> gen_;
     std::unique_ptr<RoundPrefetch<RoundData>> prefetch_;
     std::deque<RoundData> ahead_;  // generated by a worker since stopped
     int64_t next_r_ = 0;           // round after the last one handed out
@@ -818,22 +876,11 @@ py::dict NativeScheduler::next_round(int64_t r)
 {
     auto t_start0 = std::chrono::steady_clock::now();
     RoundData d;
-    if (prefetch_) {
-        if (r != next_r_)
-            throw std::invalid_argument(
-                "rounds are prefetched in order: expected round " +
-                std::to_string(next_r_) + ", got " + std::to_string(r));
-        py::gil_scoped_release nogil;
-        d = prefetch_->take(r);
-    } else if (!ahead_.empty()) {
-        if (r != next_r_)
-            throw std::invalid_argument(
-                "prefetched rounds pending: expected round " +
-                std::to_string(next_r_) + ", got " + std::to_string(r));
-        d = std::move(ahead_.front());
-        ahead_.pop_front();
+    if (prefetch_ && ahead_.empty()) {
+        py::gil_scoped_release nogil;  // only waits for the worker
+        d = fetch_round(r, false);
     } else {
-        d = compute_round(r);
+        d = fetch_round(r, false);
     }
     next_r_ = r + 1;
     auto t_mid0 = std::chrono::steady_clock::now();
@@ -849,7 +896,127 @@ py::dict NativeScheduler::next_round(int64_t r)
     return out;
 }
 
-RoundData NativeScheduler::compute_round(int64_t r)
+RoundData NativeScheduler::fetch_round(int64_t r, bool strict)
+{
+    if (!ahead_.empty()) {
+        if (r != next_r_)
+            throw std::invalid_argument(
+                "prefetched rounds pending: expected round " +
+                std::to_string(next_r_) + ", got " + std::to_string(r));
+        RoundData d = std::move(ahead_.front());
+        ahead_.pop_front();
+        return d;
+    }
+    if (prefetch_) {
+        if (r != next_r_)
+            throw std::invalid_argument(
+                "rounds are prefetched in order: expected round " +
+                std::to_string(next_r_) + ", got " + std::to_string(r));
+        return prefetch_->take(r);
+    }
+    if (strict && r != next_r_)
+        throw std::invalid_argument(
+            "rounds are taken in order: expected round " +
+            std::to_string(next_r_) + ", got " + std::to_string(r));
+    return compute_round(r);
+}
+
+static void view_of(const RoundData& d, RoundView* v)
+{
+    const PackedRound& p = d.packed;
+    auto span = [](const std::vector<int32_t>& a) {
+        return RoundSpan{a.empty() ? nullptr : a.data(), a.size()};
+    };
+    const RoundSpan none{nullptr, 0};
+    v->arrays[RA_SNAP_NODES] = span(p.snap_nodes);
+    v->arrays[RA_SNAP_SLOTS] = span(p.snap_slots);
+    v->arrays[RA_RECV_NODES] = span(p.recv_nodes);
+    v->arrays[RA_RECV_NPTR] = span(p.recv_nptr);
+    v->arrays[RA_DEL_SLOTS] = span(p.del_slots);
+    v->arrays[RA_REPLY_SLOTS] = span(p.reply_slots);
+    v->arrays[RA_PULL_NODES] = none;  // packed rounds embed the pulls
+    v->arrays[RA_PULL_SLOTS] = none;
+    v->arrays[RA_REP_NODES] = span(p.rep_nodes);
+    v->arrays[RA_REP_NPTR] = span(p.rep_nptr);
+    v->arrays[RA_REP_SLOTS] = span(p.rep_slots);
+    v->arrays[RA_DEL_PIDS] = span(p.del_pids);
+    v->arrays[RA_REP_PIDS] = span(p.rep_pids);
+    v->arrays[RA_REP_REPLY_SLOTS] = span(p.rep_reply_slots);
+    v->tptr[RT_SNAP] = span(p.snap_tptr);
+    v->tptr[RT_RECV] = span(p.recv_tptr);
+    v->tptr[RT_PULL] = span(p.pull_tptr);
+    v->tptr[RT_REP] = span(p.rep_tptr);
+    v->sent = d.sent;
+    v->failed = d.failed;
+    v->total_size = d.total_size;
+    v->n_slots = d.n_slots;
+    v->eval_nodes = d.eval_nodes.empty() ? nullptr : d.eval_nodes.data();
+    v->n_eval = d.eval_nodes.size();
+}
+
+void NativeScheduler::take_view(int64_t r, RoundView* out)
+{
+    held_ = fetch_round(r, true);
+    next_r_ = r + 1;
+    view_of(held_, out);
+}
+
+int NativeScheduler::take_thunk(void* self, int64_t r, RoundView* out,
+                                char* err, size_t errlen)
+{
+    try {
+        static_cast<NativeScheduler*>(self)->take_view(r, out);
+        return 0;
+    } catch (const std::exception& e) {
+        if (err && errlen) snprintf(err, errlen, "%s", e.what());
+    } catch (...) {
+        if (err && errlen) snprintf(err, errlen, "unknown scheduler error");
+    }
+    return 1;
+}
+
+py::tuple NativeScheduler::next_round_packed_into(int64_t r,
+                                                  py::array_t<int32_t> buf)
+{
+    if (buf.ndim() != 1 || !buf.writeable() ||
+        !(buf.flags() & py::array::c_style))
+        throw std::invalid_argument(
+            "buf must be a writeable, contiguous 1-d int32 array");
+    RoundData d;
+    {
+        py::gil_scoped_release nogil;
+        d = fetch_round(r, true);
+    }
+    RoundView v;
+    view_of(d, &v);
+    RoundLayout lay;
+    if (!write_round_layout(v, 0, buf.mutable_data(), (size_t)buf.size(),
+                            &lay)) {
+        size_t need = round_layout_capacity(v);
+        ahead_.push_front(std::move(d));  // hand it back: still round r
+        throw std::invalid_argument(
+            "buf holds " + std::to_string(buf.size()) +
+            " elements, round " + std::to_string(r) + " needs " +
+            std::to_string(need));
+    }
+    next_r_ = r + 1;
+    py::list lens, tptrs;
+    for (int i = 0; i < ROUND_N_ARRAYS; ++i) lens.append(lay.len[i]);
+    for (int i = 0; i < ROUND_N_TPTRS; ++i) {
+        auto a = py::array_t<int32_t>((py::ssize_t)v.tptr[i].len);
+        std::copy(v.tptr[i].data, v.tptr[i].data + v.tptr[i].len,
+                  a.mutable_data());
+        tptrs.append(a);
+    }
+    auto ids = py::array_t<int32_t>((py::ssize_t)lay.n_eval);
+    std::copy(buf.data() + lay.eval_off,
+              buf.data() + lay.eval_off + lay.n_eval, ids.mutable_data());
+    return py::make_tuple(
+        lens, tptrs, py::make_tuple(d.sent, d.failed, d.total_size, d.n_slots),
+        ids);
+}
+
+RoundData NativeScheduler::generate_round(int64_t r)
 {
     const int64_t t0 = r * delta_, t1 = (r + 1) * delta_;
     RoundData rd;
@@ -1058,17 +1225,32 @@ RoundData NativeScheduler::compute_round(int64_t r)
     }
 
     rd.n_slots = next_slot_;
-    rd.packed = pack_round_compute(
-        snap_nodes, snap_slots, snap_tptr, recv_nodes, recv_nptr,
-        recv_tptr, del_slots, reply_slots, del_pids, pull_nodes,
-        pull_slots, pull_tptr, rep_nodes, rep_nptr, rep_tptr, rep_slots,
-        rep_pids, del_owners, rep_owners, n_, next_slot_);
     if (sampling_eval_ > 0) {
         Stream g(stream_key(seed_, EVAL, (uint64_t)(t1 - 1), 0));
         int64_t k = std::max<int64_t>((int64_t)(n_ * sampling_eval_), 1);
         rd.eval_nodes.resize(k);
         for (int64_t i = 0; i < k; ++i) rd.eval_nodes[i] = g.integers(0, n_);
     }
+    return rd;
+}
+
+// The second half of a round: a pure function of the generated events (it
+// touches no scheduler state), so a second worker may run it while the
+// first already generates the next round.
+void NativeScheduler::pack_generated(RoundData& rd, int64_t n_nodes)
+{
+    rd.packed = pack_round_compute(
+        rd.snap_nodes, rd.snap_slots, rd.snap_tptr, rd.recv_nodes,
+        rd.recv_nptr, rd.recv_tptr, rd.del_slots, rd.reply_slots,
+        rd.del_pids, rd.pull_nodes, rd.pull_slots, rd.pull_tptr,
+        rd.rep_nodes, rd.rep_nptr, rd.rep_tptr, rd.rep_slots, rd.rep_pids,
+        rd.del_owners, rd.rep_owners, n_nodes, rd.n_slots);
+}
+
+RoundData NativeScheduler::compute_round(int64_t r)
+{
+    RoundData rd = generate_round(r);
+    pack_generated(rd, n_);
     return rd;
 }
 
@@ -1604,6 +1786,12 @@ PYBIND11_MODULE(_gossip_sched, m)
              py::arg("peers_indptr"), py::arg("peers_indices"),
              py::arg("n_parts") = 0, py::arg("sampled") = false)
         .def("next_round", &NativeScheduler::next_round)
+        .def("next_round_packed_into",
+             &NativeScheduler::next_round_packed_into, py::arg("r"),
+             py::arg("buf"))
+        // the capsule points into the scheduler, which must outlive
+        // every user of it (the runner holds both)
+        .def("round_source", &NativeScheduler::round_source)
         .def("set_lean", &NativeScheduler::set_lean)
         .def("set_prefetch", &NativeScheduler::set_prefetch);
     py::class_<NativeTokenizedScheduler>(m, "NativeTokenizedScheduler")

@@ -71,6 +71,23 @@ _MODE_ID = {
 }
 
 
+def metric_rows_to_dicts(rows) -> list:
+    """Metric dicts from the eval kernel's ``[R, 5]`` rows (accuracy,
+    precision, recall, f1, auc; a negative auc means undefined)."""
+    res = []
+    for row in rows:
+        d = {
+            "accuracy": float(row[0]),
+            "precision": float(row[1]),
+            "recall": float(row[2]),
+            "f1_score": float(row[3]),
+        }
+        if row[4] >= 0:
+            d["auc"] = float(row[4])
+        res.append(d)
+    return res
+
+
 class TorchBackend:
     """Eager PyTorch implementation (CPU oracle)."""
 
@@ -1666,18 +1683,7 @@ class HIPBackend(TorchBackend):
         (same values as :meth:`eval_metrics_fast`)."""
         buf, ev, valid = handle
         ev.synchronize()
-        res = []
-        for row in buf.numpy()[:valid]:
-            d = {
-                "accuracy": float(row[0]),
-                "precision": float(row[1]),
-                "recall": float(row[2]),
-                "f1_score": float(row[3]),
-            }
-            if row[4] >= 0:
-                d["auc"] = float(row[4])
-            res.append(d)
-        return res
+        return metric_rows_to_dicts(buf.numpy()[:valid])
 
     def eval_metrics_fast(self, state, spec, local_ids, gx, gy):
         """One-launch K13 evaluation for affine/margin families; returns a
@@ -1717,19 +1723,7 @@ class HIPBackend(TorchBackend):
             )
         else:
             return None
-        vals = out.cpu().numpy()
-        res = []
-        for row in vals:
-            d = {
-                "accuracy": float(row[0]),
-                "precision": float(row[1]),
-                "recall": float(row[2]),
-                "f1_score": float(row[3]),
-            }
-            if row[4] >= 0:
-                d["auc"] = float(row[4])
-            res.append(d)
-        return res
+        return metric_rows_to_dicts(out.cpu().numpy())
 
     def _part_dev(self, spec, dev):
         """(perm, ptr, arena_part) as int32 device tensors (cached)."""

@@ -1295,8 +1295,19 @@ class BatchedGossipSimulator(SimulationEventSender):
             *leading(tp), *args, views["rep_reply_slots"]
         )
 
+    #: ``False`` keeps the fast path's rounds on the Python round path even
+    #: where the native round driver applies (see :meth:`_round_driver`)
+    use_round_driver = True
+
     def start(self, n_rounds: int = 100) -> None:
-        """Run ``n_rounds`` rounds."""
+        """Run ``n_rounds`` rounds.
+
+        On the single-GPU fast path, logreg / pegasos / adaline rounds with
+        the pipelined global-set evaluation run through the extension's
+        native round driver, which bypasses ``_run_round_fast`` and
+        ``_evaluate``. Overriding or wrapping either of the two, setting
+        ``use_round_driver = False`` or ``GOSSIPY_NO_ROUND_DRIVER=1`` keeps
+        the Python round path (same results, slower)."""
         assert self.initialized, "call init_nodes() first"
         fast = self._fast_path_ok()
         if (
@@ -1333,8 +1344,12 @@ class BatchedGossipSimulator(SimulationEventSender):
             self._exec_pool = ThreadPoolExecutor(
                 1, thread_name_prefix="gossipy-exec"
             )
+        drv = self._round_driver() if fast else None
         for _ in range(n_rounds):
             r = self.rounds_done
+            if drv is not None and getattr(self, "_prefetched", None) is None:
+                self._driver_round(drv, r)
+                continue
             if fast:
                 # the scheduler is stateful (rounds must be generated exactly
                 # once, in order), so the prefetch lives on self and is keyed
@@ -1356,10 +1371,11 @@ class BatchedGossipSimulator(SimulationEventSender):
                     fut = self._exec_pool.submit(self._run_round_fast, flat)
                 else:
                     self._run_round_fast(flat)
-                s2 = self.scheduler.next_round_flat(r + 1)
-                self._prefetched = (
-                    r + 1, s2, self._maybe_merge(self.scheduler.last_flat)
-                )
+                if drv is None:
+                    s2 = self.scheduler.next_round_flat(r + 1)
+                    self._prefetched = (
+                        r + 1, s2, self._maybe_merge(self.scheduler.last_flat)
+                    )
                 if fut is not None:
                     fut.result()
             else:
@@ -1415,17 +1431,126 @@ class BatchedGossipSimulator(SimulationEventSender):
             self._evaluate(sched, (r + 1) * self.cfg.delta - 1)
             self.rounds_done += 1
             self.notify_timestep((r + 1) * self.cfg.delta - 1)
+            if drv is not None:
+                # that was the round an earlier start() on the Python path
+                # had left prefetched; its metrics are reported before any
+                # the driver produces
+                self._drain_eval()
         self._drain_eval()
+        if drv is not None:
+            self._report_driver_evals(drv.drain())
         self.notify_end()
+
+    def _round_driver(self):
+        """The extension's ``RoundDriver`` for this simulator, or ``None``
+        where the Python round path has to run: the whole round (schedule
+        hand-over, upload, tick launches, evaluation launch and metric
+        staging) then is one native call per round. It needs the packed
+        lean schedule, a family it has a plan for and the pipelined
+        global-set evaluation; ``GOSSIPY_NO_ROUND_DRIVER=1`` turns it off
+        (A/B; ``GOSSIPY_RD_NO_MAPPED_EVAL=1`` and
+        ``GOSSIPY_RD_NO_SIDE_UPLOAD=1`` turn off its two measured options
+        one by one).
+
+        The driver does the work of ``_run_round_fast`` and ``_evaluate``
+        without calling them. So a subclass that overrides either, or a
+        caller that replaces either on the instance (to count, time or
+        stub it), gets the Python path for all rounds: its hook keeps
+        being called, at the Python path's speed. Setting
+        ``use_round_driver = False`` on a simulator or a subclass opts out
+        in the same way without touching a hook.
+
+        Built on first use and rebuilt when a tensor it points at
+        was replaced."""
+        env = os.environ
+        if not (
+            env.get("GOSSIPY_NO_ROUND_DRIVER") != "1"
+            and self.use_round_driver
+            and hasattr(self.scheduler, "round_source")
+            and hasattr(self.scheduler, "set_lean")
+            and env.get("GOSSIPY_NO_MERGE") != "1"
+            and env.get("GOSSIPY_NO_PACK") != "1"
+            and env.get("GOSSIPY_COOP") != "1"
+            and not env.get("GOSSIPY_SB_MAX")
+            and self._exec_pool is None
+            and self.world == 1
+            and self.data.tx is None
+            and self.data.gx is not None
+            and self.data.gx.shape[0] <= 2048
+            and env.get("GOSSIPY_NO_EVAL_PIPE") != "1"
+            and hasattr(getattr(self.backend, "ext", None), "RoundDriver")
+            # the driver replaces these two hooks: a subclass that overrides
+            # one, or a caller that wrapped one on the instance, keeps
+            # being called
+            and getattr(self._run_round_fast, "__func__", None)
+            is BatchedGossipSimulator._run_round_fast
+            and getattr(self._evaluate, "__func__", None)
+            is BatchedGossipSimulator._evaluate
+        ):
+            return None
+        name, plan, _ = self.backend._family_call(self.spec, self.device)
+        if name not in ("logreg", "linear"):
+            return None
+        st, d = self.state, self.data
+        key = (
+            name, tuple(plan), id(self.scheduler),
+            *(t.data_ptr() for t in (st.params, st.ages, d.x, d.y, d.counts,
+                                     d.gx, d.gy)),
+        )
+        if getattr(self, "_rd_key", None) != key:
+            self._rd = self.backend.ext.RoundDriver(
+                st.params, st.ages, self.pool.slots, self.pool.slot_ages,
+                d.x, d.y, d.counts, d.gx, d.gy, name, tuple(plan),
+                self.scheduler.round_source(),
+                eval_all=not self.cfg.sampling_eval > 0,
+                mapped_metrics=env.get("GOSSIPY_RD_NO_MAPPED_EVAL") != "1",
+                side_upload=env.get("GOSSIPY_RD_NO_SIDE_UPLOAD") != "1",
+            )
+            self._rd_key = key
+            self._rd_pool = self.pool.slots
+        elif self._rd_pool is not self.pool.slots:
+            self._rd.set_pool(self.pool.slots, self.pool.slot_ages)
+            self._rd_pool = self.pool.slots
+        return self._rd
+
+    def _driver_round(self, drv, r: int) -> None:
+        """One round through the native driver, with the bookkeeping the
+        Python path does around ``_run_round_fast`` and ``_evaluate``."""
+        res = drv.step(r)
+        if res[4] < 0:
+            # the round needs a bigger pool: nothing ran, the driver holds it
+            self.pool.ensure(res[3])
+            drv.set_pool(self.pool.slots, self.pool.slot_ages)
+            self._rd_pool = self.pool.slots
+            res = drv.step(r)
+        t = getattr(self, "merge_stats", (0, 0))
+        self.merge_stats = (t[0] + self.cfg.delta, t[1] + drv.last_groups)
+        self._add_message_counts(res[0], res[1], res[2])
+        self._report_driver_evals(drv.poll_eval(False))
+        self.rounds_done += 1
+        self.notify_timestep((r + 1) * self.cfg.delta - 1)
+
+    def _report_driver_evals(self, blocks) -> None:
+        from .backend import metric_rows_to_dicts
+
+        for r0, rows in blocks:
+            self.notify_evaluation(
+                (r0 + 1) * self.cfg.delta - 1, False, metric_rows_to_dicts(rows)
+            )
 
     def notify_message_counts(self, sched: RoundSchedule) -> None:
         """Feed the schedule's message accounting to the observers through
         the standard update_message interface."""
+        self._add_message_counts(
+            sched.sent_messages, sched.failed_messages, sched.total_size
+        )
+
+    def _add_message_counts(self, sent: int, failed: int, size: int) -> None:
         for er in self._receivers:
             if hasattr(er, "_sent_messages"):
-                er._sent_messages += sched.sent_messages
-                er._failed_messages += sched.failed_messages
-                er._total_size += sched.total_size
+                er._sent_messages += sent
+                er._failed_messages += failed
+                er._total_size += size
 
     # -- state access for tests / checkpointing ------------------------------
 
@@ -1456,6 +1581,8 @@ class BatchedGossipSimulator(SimulationEventSender):
         implementation (python or native C++).
         """
         self._drain_eval()
+        if getattr(self, "_rd", None) is not None:
+            self._report_driver_evals(self._rd.drain())
         import dill
 
         blob = {

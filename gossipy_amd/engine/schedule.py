@@ -1679,10 +1679,22 @@ NativeSchedulerAdapter.set_lean = _adapter_set_lean
 
 
 def _adapter_set_prefetch(self, v: bool) -> None:
-    """Generate rounds on the native scheduler's own worker thread, up to
-    two ahead; ``next_round*`` then only waits and converts, and rounds must
-    be asked for in order. Pure C++ on the worker: no GIL hand-offs."""
+    """Generate rounds on the native scheduler's own worker threads (one
+    runs the tick loop, the next packs its rounds; each runs up to two
+    rounds ahead); ``next_round*`` then only waits and converts, and rounds
+    must be asked for in order. Pure C++ on the workers: no GIL hand-offs."""
     self._native.set_prefetch(v)
 
 
 NativeSchedulerAdapter.set_prefetch = _adapter_set_prefetch
+
+
+def _adapter_round_source(self):
+    """Capsule over the native scheduler's ``RoundSource`` (csrc/
+    round_source.h): what the extension's ``RoundDriver`` takes its rounds
+    from, without the GIL and without Python objects. It draws from the
+    same sequence as ``next_round*``. The adapter must outlive its users."""
+    return self._native.round_source()
+
+
+NativeSchedulerAdapter.round_source = _adapter_round_source

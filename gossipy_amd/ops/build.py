@@ -132,6 +132,8 @@ def build(verbose: bool = False) -> str:
         name="_gossip_hip",
         sources=[src],
         build_directory=build_dir,
+        # the plain-C++ headers the round driver shares with the scheduler
+        extra_include_paths=[os.path.abspath(os.path.join(here, "..", "csrc"))],
         extra_cuda_cflags=["-O3", "--offload-arch=gfx950"],
         verbose=verbose,
         is_python_module=False,

@@ -37,9 +37,21 @@
 // parameters are read from HBM once per tick and written once.
 
 #include <torch/extension.h>
+#include <pybind11/numpy.h>
 #include <ATen/hip/HIPContext.h>
 #include <hip/hip_runtime.h>
 #include <hip/hip_cooperative_groups.h>
+
+#include <atomic>
+#include <chrono>
+#include <deque>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "round_layout.h"
+#include "round_ring.h"
+#include "round_source.h"
 
 #define DEV_INLINE __device__ __forceinline__
 
@@ -3351,6 +3363,24 @@ void tick_pens(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
                        current_stream(), a);
 }
 
+// Scoring-mode launch geometry from a.D, a.d and a.n_eval: sets a.tile and
+// returns the dynamic LDS.
+// LDS: model + scores + their label-compacted copy + binarized labels
+// + confusion + one X tile.
+// The tile size adapts so everything fits the 160 KB budget.
+static size_t eval_tile_smem(EvalArgs& a)
+{
+    int n_eval = a.n_eval, d = a.d;
+    size_t fixed = sizeof(float) * (a.D + 2 * (size_t)n_eval)
+        + ((n_eval + 15) & ~15) * sizeof(char)
+        + sizeof(int) * EVAL_KMAX * EVAL_KMAX;
+    long room = (long)(160 * 1024 - fixed) / (long)(sizeof(float) * d);
+    TORCH_CHECK(room >= 16, "eval LDS budget exceeded (n_eval=", n_eval,
+                ", d=", d, ")");
+    a.tile = (int)std::min<long>({room, (long)n_eval, 512});
+    return fixed + sizeof(float) * (size_t)a.tile * d;
+}
+
 torch::Tensor eval_metrics(torch::Tensor params, torch::Tensor nodes,
                            torch::Tensor X, torch::Tensor Y, int64_t d,
                            int64_t k, bool is_margin,
@@ -3373,17 +3403,7 @@ torch::Tensor eval_metrics(torch::Tensor params, torch::Tensor nodes,
     a.is_margin = is_margin;
     a.scores = nullptr;
     a.eval_counts = per_node ? eval_counts.data_ptr<int>() : nullptr;
-    // LDS: model + scores + their label-compacted copy + binarized labels
-    // + confusion + one X tile.
-    // The tile size adapts so everything fits the 160 KB budget.
-    size_t fixed = sizeof(float) * (a.D + 2 * (size_t)n_eval)
-        + ((n_eval + 15) & ~15) * sizeof(char)
-        + sizeof(int) * EVAL_KMAX * EVAL_KMAX;
-    long room = (long)(160 * 1024 - fixed) / (long)(sizeof(float) * d);
-    TORCH_CHECK(room >= 16, "eval LDS budget exceeded (n_eval=", n_eval,
-                ", d=", d, ")");
-    a.tile = (int)std::min<long>({room, (long)n_eval, 512});
-    size_t smem = fixed + sizeof(float) * (size_t)a.tile * d;
+    size_t smem = eval_tile_smem(a);
     hipLaunchKernelGGL(eval_metrics_kernel, dim3(R), dim3(256), smem,
                        current_stream(), a);
     return out;
@@ -3420,8 +3440,600 @@ torch::Tensor eval_metrics_scores(torch::Tensor scores, torch::Tensor Y,
     return out;
 }
 
+// ---------------------------------------------------------------------------
+// RoundDriver: one native call per round. It takes the round from the
+// scheduler's RoundSource (csrc/round_source.h), writes the upload layout
+// (csrc/round_layout.h) into pinned memory, issues the one H2D copy, runs
+// stream_round over pointers into the device copy, and launches the round's
+// evaluation with its node ids read from the same upload. Nothing of the
+// schedule becomes a Python object.
+//
+// Ownership: the driver owns a ring of RD_RING upload slots (pinned host
+// buffer + device buffer + event) and two metric staging buffers (pinned
+// host + event). A slot's event is recorded after the last work of its
+// round that reads the slot; the slot is rewritten, grown or freed only
+// after that event completed. The state, pool and eval tensors are held by
+// reference; the pool is replaced through set_pool() when it grows.
+//
+// Two measured options, both on by default (profiles/round_driver.md):
+// mapped_metrics: the eval kernel writes its [R, 5] rows straight into the
+//   device-mapped staging buffer, so no D2H copy is dispatched (off: the
+//   rows go to a device buffer the driver owns and are copied out);
+// side_upload: the H2D copy runs on a stream of the driver's own and the
+//   compute stream waits for its event, which takes the copy off the
+//   kernels' chain.
+// ---------------------------------------------------------------------------
+
+#define RD_CHECK(expr)                                                     \
+    do {                                                                   \
+        hipError_t rd_err_ = (expr);                                       \
+        if (rd_err_ != hipSuccess)                                         \
+            throw std::runtime_error(std::string(#expr " failed: ") +      \
+                                     hipGetErrorString(rd_err_));          \
+    } while (0)
+
+constexpr int RD_RING = 4;
+
+// What the drivers of this process hold right now: pinned host buffers,
+// device buffers, events, streams. Counted where each is created and
+// destroyed, so a test can see that a destroyed driver released everything.
+static std::atomic<int64_t> rd_live[4];
+enum { RD_HOST = 0, RD_DEV, RD_EVENT, RD_STREAM };
+
+static void rd_host_alloc(void** p, size_t bytes, unsigned flags)
+{
+    RD_CHECK(hipHostMalloc(p, bytes, flags));
+    ++rd_live[RD_HOST];
+}
+static hipError_t rd_host_free(void* p)
+{
+    --rd_live[RD_HOST];
+    return hipHostFree(p);
+}
+static void rd_dev_alloc(void** p, size_t bytes)
+{
+    RD_CHECK(hipMalloc(p, bytes));
+    ++rd_live[RD_DEV];
+}
+static hipError_t rd_dev_free(void* p)
+{
+    --rd_live[RD_DEV];
+    return hipFree(p);
+}
+static void rd_event_create(hipEvent_t* e)
+{
+    RD_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    ++rd_live[RD_EVENT];
+}
+static void rd_event_destroy(hipEvent_t e)
+{
+    --rd_live[RD_EVENT];
+    (void)hipEventDestroy(e);
+}
+
+static py::tuple round_driver_live()
+{
+    return py::make_tuple(rd_live[RD_HOST].load(), rd_live[RD_DEV].load(),
+                          rd_live[RD_EVENT].load(), rd_live[RD_STREAM].load());
+}
+
+class RoundDriver {
+public:
+    RoundDriver(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
+                torch::Tensor slot_ages, torch::Tensor X, torch::Tensor Y,
+                torch::Tensor counts, torch::Tensor gx, torch::Tensor gy,
+                const std::string& family, py::tuple plan, py::capsule source,
+                bool eval_all, bool mapped_metrics, bool side_upload)
+        : st_{params, ages, slots, slot_ages, X, Y, counts}, gx_(gx), gy_(gy),
+          source_cap_(source), eval_all_(eval_all), mapped_(mapped_metrics),
+          side_upload_(side_upload)
+    {
+        TORCH_CHECK(std::string(source.name() ? source.name() : "") ==
+                        "gossipy_amd.RoundSource",
+                    "source must be NativeScheduler.round_source()");
+        src_ = *static_cast<const RoundSource*>(source.get_pointer());
+        CHECK_DEV(gx); CHECK_DEV(gy);
+        if (family == "logreg") {
+            TORCH_CHECK(plan.size() == 7 || plan.size() == 8,
+                        "logreg plan: (d, k, lr, wd, epochs, bs, mode"
+                        "[, merge_limit])");
+            lg_ = logreg_plan(
+                st_, plan[0].cast<int64_t>(), plan[1].cast<int64_t>(),
+                plan[2].cast<double>(), plan[3].cast<double>(),
+                plan[4].cast<int64_t>(), plan[5].cast<int64_t>(),
+                plan[6].cast<int64_t>(),
+                plan.size() == 8 ? plan[7].cast<int64_t>() : -1);
+            ev_.d = lg_.a.d; ev_.k = lg_.a.k; ev_.is_margin = 0;
+        } else if (family == "linear") {
+            TORCH_CHECK(plan.size() == 4,
+                        "linear plan: (d, lrlam, is_pegasos, mode)");
+            linear_ = true;
+            ln_ = linear_plan(st_, plan[0].cast<int64_t>(),
+                              plan[1].cast<double>(), plan[2].cast<int64_t>(),
+                              plan[3].cast<int64_t>());
+            ev_.d = ln_.a.d; ev_.k = 1; ev_.is_margin = 1;
+        } else {
+            TORCH_CHECK(false, "RoundDriver: unsupported family ", family);
+        }
+        TORCH_CHECK(ev_.k <= EVAL_KMAX, "n_classes > ", EVAL_KMAX,
+                    " unsupported");
+        TORCH_CHECK(gx.dim() == 2 && gx.size(1) == ev_.d &&
+                        gx.scalar_type() == torch::kFloat32,
+                    "gx must be float32 [n_eval, d]");
+        TORCH_CHECK(gy.dim() == 1 && gy.size(0) == gx.size(0) &&
+                        gy.scalar_type() == torch::kFloat32,
+                    "gy must be float32 [n_eval]");
+        const SnapGeom& g = snap_geom();
+        TORCH_CHECK(params.dim() == 2 && params.size(1) == g.Dp &&
+                        params.scalar_type() == torch::kFloat32,
+                    "params must be float32 [n, ", g.Dp, "]");
+        TORCH_CHECK(ages.is_cuda() && ages.is_contiguous() &&
+                        ages.scalar_type() == torch::kInt32 &&
+                        ages.dim() == 1 && ages.size(0) == params.size(0),
+                    "ages must be int32 [n] on device");
+        check_pool(slots, slot_ages);
+        ev_.params = params.data_ptr<float>();
+        ev_.X = gx.data_ptr<float>();
+        ev_.Y = gy.data_ptr<float>();
+        ev_.n_eval = (int)gx.size(0);
+        ev_.D = (int)params.size(1);
+        ev_.scores = nullptr;
+        ev_.eval_counts = nullptr;
+        ev_smem_ = eval_tile_smem(ev_);
+        n_local_ = params.size(0);
+        pool_cap_ = slots.size(0);
+        try {
+            for (auto& s : ring_)
+                rd_event_create(&s.ev);
+            for (auto& m : stage_)
+                rd_event_create(&m.ev);
+            if (side_upload_) {
+                RD_CHECK(hipStreamCreateWithFlags(&up_stream_,
+                                                  hipStreamNonBlocking));
+                ++rd_live[RD_STREAM];
+                rd_event_create(&up_ev_);
+            }
+        } catch (...) {
+            release();
+            throw;
+        }
+    }
+
+    RoundDriver(const RoundDriver&) = delete;
+    RoundDriver& operator=(const RoundDriver&) = delete;
+
+    ~RoundDriver() { release(); }
+
+    // The pool was replaced (SlotPool.ensure grew it).
+    void set_pool(torch::Tensor slots, torch::Tensor slot_ages)
+    {
+        check_pool(slots, slot_ages);
+        st_.slots = slots; st_.slot_ages = slot_ages;
+        auto set = [&](auto& a) {
+            a.slots = slots.data_ptr<float>();
+            a.slot_ages = slot_ages.data_ptr<int>();
+        };
+        if (linear_) set(ln_.a); else set(lg_.a);
+        pool_cap_ = slots.size(0);
+    }
+
+    // Runs round r. Returns (sent, failed, total_size, n_slots, n_eval_rows).
+    // n_eval_rows == -1: the round needs n_slots pool slots and the pool is
+    // smaller; nothing was enqueued and the round is held. Grow the pool,
+    // call set_pool() and call step(r) again.
+    py::tuple step(int64_t r)
+    {
+        int64_t rows = 0;
+        {
+            py::gil_scoped_release nogil;
+            if (failed_)
+                throw std::runtime_error(
+                    "RoundDriver: an earlier step failed; nothing more is "
+                    "enqueued");
+            if (!(held_ && held_r_ == r)) {
+                if (held_)
+                    throw std::runtime_error(
+                        "RoundDriver: round " + std::to_string(held_r_) +
+                        " is held, got step(" + std::to_string(r) + ")");
+                char err[256] = {0};
+                auto t0 = std::chrono::steady_clock::now();
+                if (src_.take(src_.self, r, &view_, err, sizeof(err)))
+                    throw std::invalid_argument(err);
+                take_s_ += seconds_since(t0);
+                held_ = true;
+                held_r_ = r;
+            }
+            if (view_.n_slots > pool_cap_) {
+                rows = -1;
+            } else {
+                auto t0 = std::chrono::steady_clock::now();
+                try {
+                    rows = run_held();
+                } catch (...) {
+                    failed_ = true;
+                    throw;
+                }
+                enqueue_s_ += seconds_since(t0);
+                ++rounds_;
+                held_ = false;
+            }
+        }
+        return py::make_tuple(view_.sent, view_.failed, view_.total_size,
+                              view_.n_slots, rows);
+    }
+
+    // The launch groups of the last round run (a perf-probe counter).
+    int64_t last_groups() const { return last_groups_; }
+
+    // Where step() spent its time so far, for the perf probes: seconds
+    // waiting in the source's take(), seconds writing the layout and
+    // enqueueing (waits for a busy ring slot or a due evaluation included),
+    // and the rounds run.
+    py::tuple stats() const
+    {
+        return py::make_tuple(take_s_, enqueue_s_, rounds_);
+    }
+
+    // Completed evaluations as (round, float32[R, 5]), oldest first. The
+    // rule of the runner's _drain_eval: without `force` only what has
+    // already arrived is collected, except that two in flight make the
+    // older one due.
+    py::list poll_eval(bool force)
+    {
+        {
+            py::gil_scoped_release nogil;
+            while (!pending_.empty()) {
+                Stage& m = stage_[pending_.front()];
+                if (!force && pending_.size() < 2) {
+                    hipError_t q = hipEventQuery(m.ev);
+                    if (q == hipErrorNotReady) break;
+                    RD_CHECK(q);
+                }
+                collect_oldest();
+            }
+        }
+        py::list out;
+        for (auto& d : done_) {
+            auto a = py::array_t<float>({(py::ssize_t)d.rows, (py::ssize_t)5});
+            std::copy(d.vals.begin(), d.vals.end(), a.mutable_data());
+            out.append(py::make_tuple(d.round, a));
+        }
+        done_.clear();
+        return out;
+    }
+
+    py::list drain() { return poll_eval(true); }
+
+private:
+    struct Slot {
+        int32_t* h = nullptr;
+        int32_t* d = nullptr;
+        size_t cap = 0;
+        hipEvent_t ev = nullptr;
+    };
+    struct Stage {
+        float* h = nullptr;      // pinned; the kernel's target when mapped
+        float* h_dev = nullptr;  // its device address
+        size_t cap_rows = 0;
+        hipEvent_t ev = nullptr;
+        int64_t round = 0;
+        int64_t rows = 0;
+    };
+    struct Done {
+        int64_t round, rows;
+        std::vector<float> vals;
+    };
+
+    const SnapGeom& snap_geom() const { return linear_ ? ln_.snap : lg_.snap; }
+
+    // A pool the plan's kernels can write: rows as wide as a snapshot, one
+    // int32 age per slot. The snapshot kernel writes snap.W floats per slot
+    // row, so any other width would run past the pool's end.
+    void check_pool(const torch::Tensor& slots,
+                    const torch::Tensor& slot_ages) const
+    {
+        const SnapGeom& g = snap_geom();
+        TORCH_CHECK(slots.is_cuda() && slots.is_contiguous() &&
+                        slots.scalar_type() == torch::kFloat32 &&
+                        slots.dim() == 2 && slots.size(1) == g.W,
+                    "pool slots must be contiguous float32 [capacity, ", g.W,
+                    "] on device");
+        TORCH_CHECK(g.age_w == 1 && slot_ages.is_cuda() &&
+                        slot_ages.is_contiguous() &&
+                        slot_ages.scalar_type() == torch::kInt32 &&
+                        slot_ages.dim() == 1 &&
+                        slot_ages.size(0) == slots.size(0),
+                    "pool slot_ages must be contiguous int32 [capacity] on "
+                    "device");
+    }
+
+    static double seconds_since(std::chrono::steady_clock::time_point t0)
+    {
+        return std::chrono::duration<double>(
+                   std::chrono::steady_clock::now() - t0).count();
+    }
+
+    void collect_oldest()
+    {
+        Stage& m = stage_[pending_.front()];
+        RD_CHECK(hipEventSynchronize(m.ev));
+        Done d{m.round, m.rows, {}};
+        d.vals.assign(m.h, m.h + m.rows * 5);
+        done_.push_back(std::move(d));
+        pending_.pop_front();
+    }
+
+    void grow_slot(Slot& s, size_t need)
+    {
+        size_t cap = grown_capacity(s.cap, need);
+        if (cap == s.cap) return;
+        // the slot's event has completed: nothing reads the old buffers
+        if (s.h) RD_CHECK(rd_host_free(s.h));
+        s.h = nullptr; s.cap = 0;
+        if (s.d) RD_CHECK(rd_dev_free(s.d));
+        s.d = nullptr;
+        rd_host_alloc((void**)&s.h, cap * sizeof(int32_t), hipHostMallocDefault);
+        rd_dev_alloc((void**)&s.d, cap * sizeof(int32_t));
+        s.cap = cap;
+    }
+
+    void grow_stage(Stage& m, size_t rows)
+    {
+        size_t cap = grown_capacity(m.cap_rows, rows);
+        if (cap == m.cap_rows) return;
+        if (m.h) RD_CHECK(rd_host_free(m.h));
+        m.h = nullptr; m.cap_rows = 0;
+        rd_host_alloc((void**)&m.h, cap * 5 * sizeof(float), hipHostMallocMapped);
+        RD_CHECK(hipHostGetDevicePointer((void**)&m.h_dev, m.h, 0));
+        m.cap_rows = cap;
+    }
+
+    // enqueue the held round; returns the rows its evaluation will have
+    int64_t run_held()
+    {
+        hipStream_t s = current_stream();
+        const RoundView& v = view_;
+        // the old metrics go first: a third evaluation needs their staging
+        int64_t n_ids_max = (int64_t)v.n_eval;
+        bool will_eval = n_ids_max > 0 || eval_all_;
+        if (will_eval && pending_.size() >= 2) collect_oldest();
+
+        int si = slots_.acquire(
+            [&](int i) {
+                hipError_t q = hipEventQuery(ring_[i].ev);
+                if (q != hipErrorNotReady) RD_CHECK(q);
+                return q == hipSuccess;
+            },
+            [&](int i) { RD_CHECK(hipEventSynchronize(ring_[i].ev)); });
+        Slot& sl = ring_[si];
+        bool recorded = false;
+        try {
+            grow_slot(sl, round_layout_capacity(v));
+            RoundLayout lay;
+            if (!write_round_layout(v, 0, sl.h, sl.cap, &lay))
+                throw std::runtime_error("RoundDriver: upload slot too small");
+            check_bounds(v, lay, sl.h);
+            if (side_upload_) {
+                // the copy may not overtake the compute stream's reads of
+                // this device buffer four rounds ago: the slot's event has
+                // completed (acquire above), so nothing is left to wait for
+                RD_CHECK(hipMemcpyAsync(sl.d, sl.h,
+                                        lay.total * sizeof(int32_t),
+                                        hipMemcpyHostToDevice, up_stream_));
+                RD_CHECK(hipEventRecord(up_ev_, up_stream_));
+                RD_CHECK(hipStreamWaitEvent(s, up_ev_, 0));
+            } else {
+                RD_CHECK(hipMemcpyAsync(sl.d, sl.h,
+                                        lay.total * sizeof(int32_t),
+                                        hipMemcpyHostToDevice, s));
+            }
+
+            RoundArrays ra;
+            auto dp = [&](int id) -> const int* {
+                return lay.len[id] ? sl.d + lay.off[id] : nullptr;
+            };
+            ra.snap_nodes = dp(RA_SNAP_NODES); ra.snap_slots = dp(RA_SNAP_SLOTS);
+            ra.recv_nodes = dp(RA_RECV_NODES); ra.recv_nptr = dp(RA_RECV_NPTR);
+            ra.del_slots = dp(RA_DEL_SLOTS); ra.reply_slots = dp(RA_REPLY_SLOTS);
+            ra.del_pids = dp(RA_DEL_PIDS);
+            ra.pull_nodes = dp(RA_PULL_NODES); ra.pull_slots = dp(RA_PULL_SLOTS);
+            ra.rep_nodes = dp(RA_REP_NODES); ra.rep_nptr = dp(RA_REP_NPTR);
+            ra.rep_slots = dp(RA_REP_SLOTS); ra.rep_pids = dp(RA_REP_PIDS);
+            ra.rep_reply_slots = dp(RA_REP_REPLY_SLOTS);
+            ra.snap_tptr = v.tptr[RT_SNAP].data;
+            ra.recv_tptr = v.tptr[RT_RECV].data;
+            ra.pull_tptr = v.tptr[RT_PULL].data;
+            ra.rep_tptr = v.tptr[RT_REP].data;
+            ra.delta = (int)v.tptr[RT_SNAP].len - 1;
+            last_groups_ = ra.delta;
+            if (linear_) stream_round(ln_, ra); else stream_round(lg_, ra);
+            RD_CHECK(hipGetLastError());
+
+            int64_t rows = lay.n_eval ? (int64_t)lay.n_eval
+                                      : (eval_all_ ? n_local_ : 0);
+            if (rows) {
+                int mi = stage_next_;
+                Stage& m = stage_[mi];
+                grow_stage(m, (size_t)rows);
+                if (!mapped_ && (size_t)rows > d_out_rows_) {
+                    size_t cap = grown_capacity(d_out_rows_, (size_t)rows);
+                    // hipFree waits for the device: no kernel still writes it
+                    if (d_out_) RD_CHECK(rd_dev_free(d_out_));
+                    d_out_ = nullptr; d_out_rows_ = 0;
+                    rd_dev_alloc((void**)&d_out_, cap * 5 * sizeof(float));
+                    d_out_rows_ = cap;
+                }
+                EvalArgs a = ev_;
+                a.nodes = lay.n_eval ? sl.d + lay.eval_off : nullptr;
+                a.out = mapped_ ? m.h_dev : d_out_;
+                launch_kernel(eval_metrics_kernel, (int)rows, 256, ev_smem_,
+                              s, a);
+                if (!mapped_)
+                    RD_CHECK(hipMemcpyAsync(m.h, d_out_,
+                                            (size_t)rows * 5 * sizeof(float),
+                                            hipMemcpyDeviceToHost, s));
+                RD_CHECK(hipEventRecord(m.ev, s));
+                m.round = held_r_; m.rows = rows;
+                pending_.push_back(mi);
+                stage_next_ ^= 1;
+            }
+            // after the eval launch: it reads its ids from this slot
+            RD_CHECK(hipEventRecord(sl.ev, s));
+            recorded = true;
+            return rows;
+        } catch (...) {
+            if (!recorded) {
+                // what was enqueued may still read the slot: drain it
+                // before the slot counts as free again
+                (void)hipStreamSynchronize(s);
+                if (side_upload_) (void)hipStreamSynchronize(up_stream_);
+                slots_.abandon(si);
+            }
+            throw;
+        }
+    }
+
+    // Every index the kernels will follow stays inside its array: node ids
+    // below n_local, slot ids below the pool capacity (a negative reply slot
+    // means "none" to the kernels), CSR pointers and tick
+    // pointers monotone and inside their targets. One pass over a few KB of
+    // host memory; a schedule that fails it is never uploaded.
+    void check_bounds(const RoundView& v, const RoundLayout& lay,
+                      const int32_t* h) const
+    {
+        auto bad = [](const char* what) {
+            throw std::runtime_error(
+                std::string("RoundDriver: schedule out of bounds: ") + what);
+        };
+        auto all_in = [&](int id, int64_t lo, int64_t hi, const char* what) {
+            const int32_t* p = h + lay.off[id];
+            for (size_t i = 0; i < lay.len[id]; ++i)
+                if (p[i] < lo || p[i] >= hi) bad(what);
+        };
+        auto csr = [&](int id, size_t target, const char* what) {
+            const int32_t* p = h + lay.off[id];
+            if (lay.len[id] == 0 || p[0] != 0) bad(what);
+            for (size_t i = 1; i < lay.len[id]; ++i)
+                if (p[i] < p[i - 1]) bad(what);
+            if ((size_t)p[lay.len[id] - 1] > target) bad(what);
+        };
+        auto tptr = [&](int id, size_t target, size_t groups,
+                        const char* what) {
+            const RoundSpan& t = v.tptr[id];
+            if (t.len != groups + 1 || t.data[0] != 0) bad(what);
+            for (size_t i = 1; i < t.len; ++i)
+                if (t.data[i] < t.data[i - 1]) bad(what);
+            if ((size_t)t.data[t.len - 1] > target) bad(what);
+        };
+        if (v.tptr[RT_SNAP].len < 1) bad("snap_tptr");
+        size_t groups = v.tptr[RT_SNAP].len - 1;
+        all_in(RA_SNAP_NODES, 0, n_local_, "snap_nodes");
+        all_in(RA_SNAP_SLOTS, 0, pool_cap_, "snap_slots");
+        if (lay.len[RA_SNAP_SLOTS] != lay.len[RA_SNAP_NODES]) bad("snap_slots");
+        all_in(RA_RECV_NODES, 0, n_local_, "recv_nodes");
+        all_in(RA_DEL_SLOTS, 0, pool_cap_, "del_slots");
+        all_in(RA_REPLY_SLOTS, INT32_MIN, pool_cap_, "reply_slots");
+        all_in(RA_REP_NODES, 0, n_local_, "rep_nodes");
+        all_in(RA_REP_SLOTS, 0, pool_cap_, "rep_slots");
+        all_in(RA_REP_REPLY_SLOTS, INT32_MIN, pool_cap_, "rep_reply_slots");
+        if (lay.len[RA_PULL_NODES] || lay.len[RA_PULL_SLOTS])
+            bad("pull arrays in a packed round");
+        if (lay.len[RA_RECV_NPTR] != lay.len[RA_RECV_NODES] + 1) bad("recv_nptr");
+        if (lay.len[RA_REP_NPTR] != lay.len[RA_REP_NODES] + 1) bad("rep_nptr");
+        csr(RA_RECV_NPTR, lay.len[RA_DEL_SLOTS], "recv_nptr");
+        csr(RA_REP_NPTR, lay.len[RA_REP_SLOTS], "rep_nptr");
+        auto same_or_empty = [&](int id, int as, const char* what) {
+            if (lay.len[id] && lay.len[id] != lay.len[as]) bad(what);
+        };
+        same_or_empty(RA_REPLY_SLOTS, RA_DEL_SLOTS, "reply_slots");
+        same_or_empty(RA_DEL_PIDS, RA_DEL_SLOTS, "del_pids");
+        same_or_empty(RA_REP_REPLY_SLOTS, RA_REP_SLOTS, "rep_reply_slots");
+        same_or_empty(RA_REP_PIDS, RA_REP_SLOTS, "rep_pids");
+        tptr(RT_SNAP, lay.len[RA_SNAP_NODES], groups, "snap_tptr");
+        tptr(RT_RECV, lay.len[RA_RECV_NODES], groups, "recv_tptr");
+        tptr(RT_PULL, 0, groups, "pull_tptr");
+        tptr(RT_REP, lay.len[RA_REP_NODES], groups, "rep_tptr");
+        const int32_t* ids = h + lay.eval_off;
+        for (size_t i = 0; i < lay.n_eval; ++i)
+            if (ids[i] < 0 || ids[i] >= n_local_) bad("eval ids");
+    }
+
+    void release() noexcept
+    {
+        for (auto& s : ring_) {
+            if (s.ev) { (void)hipEventSynchronize(s.ev); rd_event_destroy(s.ev); }
+            if (s.h) (void)rd_host_free(s.h);
+            if (s.d) (void)rd_dev_free(s.d);
+            s = Slot{};
+        }
+        for (auto& m : stage_) {
+            if (m.ev) { (void)hipEventSynchronize(m.ev); rd_event_destroy(m.ev); }
+            if (m.h) (void)rd_host_free(m.h);
+            m = Stage{};
+        }
+        if (d_out_) (void)rd_dev_free(d_out_);
+        d_out_ = nullptr;
+        if (up_ev_) rd_event_destroy(up_ev_);
+        if (up_stream_) {
+            (void)hipStreamSynchronize(up_stream_);
+            (void)hipStreamDestroy(up_stream_);
+            --rd_live[RD_STREAM];
+        }
+        up_ev_ = nullptr; up_stream_ = nullptr;
+    }
+
+    StateTensors st_;
+    torch::Tensor gx_, gy_;
+    py::capsule source_cap_;
+    RoundSource src_{};
+    bool eval_all_, mapped_, side_upload_;
+    bool linear_ = false;
+    Plan<LogregArgs> lg_;
+    Plan<LinearArgs> ln_;
+    EvalArgs ev_{};
+    size_t ev_smem_ = 0;
+    int64_t n_local_ = 0, pool_cap_ = 0;
+
+    RoundView view_{};
+    bool held_ = false, failed_ = false;
+    int64_t held_r_ = -1, last_groups_ = 0, rounds_ = 0;
+    double take_s_ = 0, enqueue_s_ = 0;
+
+    Slot ring_[RD_RING];
+    SlotRing<RD_RING> slots_;
+    Stage stage_[2];
+    int stage_next_ = 0;
+    std::deque<int> pending_;  // staging indices in flight, oldest first
+    std::vector<Done> done_;   // collected, not yet handed to Python
+    float* d_out_ = nullptr;
+    size_t d_out_rows_ = 0;
+    hipStream_t up_stream_ = nullptr;
+    hipEvent_t up_ev_ = nullptr;
+};
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
 {
+    py::class_<RoundDriver>(m, "RoundDriver")
+        .def(py::init<torch::Tensor, torch::Tensor, torch::Tensor,
+                      torch::Tensor, torch::Tensor, torch::Tensor,
+                      torch::Tensor, torch::Tensor, torch::Tensor,
+                      const std::string&, py::tuple, py::capsule, bool, bool,
+                      bool>(),
+             py::arg("params"), py::arg("ages"), py::arg("slots"),
+             py::arg("slot_ages"), py::arg("X"), py::arg("Y"),
+             py::arg("counts"), py::arg("gx"), py::arg("gy"),
+             py::arg("family"), py::arg("plan"), py::arg("source"),
+             py::arg("eval_all") = false, py::arg("mapped_metrics") = true,
+             py::arg("side_upload") = true)
+        .def("step", &RoundDriver::step)
+        .def("set_pool", &RoundDriver::set_pool)
+        .def("poll_eval", &RoundDriver::poll_eval)
+        .def("drain", &RoundDriver::drain)
+        .def("stats", &RoundDriver::stats)
+        .def_property_readonly("last_groups", &RoundDriver::last_groups);
+    m.def("round_driver_live", &round_driver_live,
+          "(pinned host buffers, device buffers, events, streams) held by "
+          "the RoundDrivers of this process");
     m.def("snapshot", &snapshot, "batched model snapshot (arena row copy)");
     m.def("tick_logreg", &tick_logreg, "fused merge + logreg SGD tick");
     m.def("tick_logreg", &tick_logreg_lim,
