@@ -140,7 +140,10 @@ the receiver keeps its model when `a > b + L`, adopts the received one when
 `sample_size`; the PENS and all2all simulators refuse it. On HIP it runs in
 second instantiations of the logreg and MLP tick kernels, per tick and
 through the stream whole-round executor; the opt-in cooperative and
-single-workgroup rounds are not extended and are bypassed.
+single-workgroup rounds are not extended and are bypassed. The extension's
+`tick_logreg`, `tick_mlp`, `run_round_logreg` and `run_round_mlp` take the
+threshold as `merge_limit` directly after `mode`, always: `-1` is the plain
+mean.
 
 `n_parts` and `sample_size` are mutually exclusive, and `MLPSpec` rejects
 either together with `pass_through=True` (`ValueError`): PASS is an error
@@ -149,6 +152,21 @@ supported. Partitioned runs keep `[n_nodes, P]` ages. The MLP kernels hold
 the model row (two rows outside `MERGE_UPDATE`), one batch of activations
 and two gradient buffers in LDS and refuse shapes over 160 KiB per block;
 shrink `batch_size` or `hidden` when that check fires.
+
+## The extension's whole-round ops
+
+Every `run_round_<family>` op of the HIP extension starts with the same
+block: `params, ages, slots, slot_ages`, then the round as one upload
+(`round_buf`, a 1-D int32 device tensor holding the round's event arrays back
+to back, and `lens`, their lengths), then `snap_tptr, recv_tptr, pull_tptr,
+rep_tptr` (int32, on the host; on the device for `run_round_coop_logreg`),
+then `X, Y, counts`; the family's own arguments follow. Which arrays, and in
+which order, is the extension's `ROUND_ARRAY_NAMES` (14 names) and
+`ROUND_TPTR_NAMES`, exported by `_gossip_sched` as well and defined once in
+`csrc/round_source.h`. A call whose `round_buf` is not a contiguous int32
+device tensor, whose `lens` has another count, a negative entry or a sum past
+the buffer, or whose tick pointers are empty or differ in length raises
+`RuntimeError` and launches nothing.
 """
 
 

@@ -5,7 +5,7 @@
 //   [ the ROUND_N_ARRAYS packed event arrays, in RoundArrayId order ]
 //   [ the eval ids: sorted, unique, local (global id - node_lo)      ]
 //
-// which is np.concatenate over `dev_names` followed by
+// which is np.concatenate over ROUND_ARRAY_NAMES followed by
 // np.unique(eval_nodes) - node_lo.
 #pragma once
 

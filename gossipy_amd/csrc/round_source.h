@@ -10,34 +10,43 @@
 #include <cstddef>
 #include <cstdint>
 
-// The packed event arrays in the order the executors' one upload lays them
-// out (the `dev_names` of BatchedGossipSimulator._run_round_fast).
-enum RoundArrayId {
-    RA_SNAP_NODES = 0,
-    RA_SNAP_SLOTS,
-    RA_RECV_NODES,
-    RA_RECV_NPTR,
-    RA_DEL_SLOTS,
-    RA_REPLY_SLOTS,
-    RA_PULL_NODES,
-    RA_PULL_SLOTS,
-    RA_REP_NODES,
-    RA_REP_NPTR,
-    RA_REP_SLOTS,
-    RA_DEL_PIDS,
-    RA_REP_PIDS,
-    RA_REP_REPLY_SLOTS,
-    ROUND_N_ARRAYS
-};
+// The packed event arrays of a round. This table is their definition: its
+// order is the order the one upload lays them out in, and every consumer
+// (the scheduler's RoundView, the executors' RoundArrays, the Python path's
+// upload through the exported ROUND_ARRAY_NAMES) indexes by it.
+#define ROUND_ARRAY_TABLE(X)              \
+    X(RA_SNAP_NODES, "snap_nodes")        \
+    X(RA_SNAP_SLOTS, "snap_slots")        \
+    X(RA_RECV_NODES, "recv_nodes")        \
+    X(RA_RECV_NPTR, "recv_nptr")          \
+    X(RA_DEL_SLOTS, "del_slots")          \
+    X(RA_REPLY_SLOTS, "reply_slots")      \
+    X(RA_PULL_NODES, "pull_nodes")        \
+    X(RA_PULL_SLOTS, "pull_slots")        \
+    X(RA_REP_NODES, "rep_nodes")          \
+    X(RA_REP_NPTR, "rep_nptr")            \
+    X(RA_REP_SLOTS, "rep_slots")          \
+    X(RA_DEL_PIDS, "del_pids")            \
+    X(RA_REP_PIDS, "rep_pids")            \
+    X(RA_REP_REPLY_SLOTS, "rep_reply_slots")
 
 // The packed tick-pointer arrays ([n_groups + 1] each, read on the host).
-enum RoundTptrId {
-    RT_SNAP = 0,
-    RT_RECV,
-    RT_PULL,
-    RT_REP,
-    ROUND_N_TPTRS
-};
+#define ROUND_TPTR_TABLE(X)   \
+    X(RT_SNAP, "snap_tptr")   \
+    X(RT_RECV, "recv_tptr")   \
+    X(RT_PULL, "pull_tptr")   \
+    X(RT_REP, "rep_tptr")
+
+#define ROUND_TABLE_ID(id, name) id,
+#define ROUND_TABLE_NAME(id, name) name,
+enum RoundArrayId { ROUND_ARRAY_TABLE(ROUND_TABLE_ID) ROUND_N_ARRAYS };
+enum RoundTptrId { ROUND_TPTR_TABLE(ROUND_TABLE_ID) ROUND_N_TPTRS };
+static const char* const ROUND_ARRAY_NAMES[ROUND_N_ARRAYS] = {
+    ROUND_ARRAY_TABLE(ROUND_TABLE_NAME)};
+static const char* const ROUND_TPTR_NAMES[ROUND_N_TPTRS] = {
+    ROUND_TPTR_TABLE(ROUND_TABLE_NAME)};
+#undef ROUND_TABLE_ID
+#undef ROUND_TABLE_NAME
 
 struct RoundSpan {
     const int32_t* data;

@@ -1774,6 +1774,12 @@ py::dict NativeTokenizedScheduler::next_round(int64_t r)
 
 PYBIND11_MODULE(_gossip_sched, m)
 {
+    // the table of round_source.h: the upload order, by name
+    py::tuple arrays((size_t)ROUND_N_ARRAYS), tptrs((size_t)ROUND_N_TPTRS);
+    for (int i = 0; i < ROUND_N_ARRAYS; ++i) arrays[i] = ROUND_ARRAY_NAMES[i];
+    for (int i = 0; i < ROUND_N_TPTRS; ++i) tptrs[i] = ROUND_TPTR_NAMES[i];
+    m.attr("ROUND_ARRAY_NAMES") = arrays;
+    m.attr("ROUND_TPTR_NAMES") = tptrs;
     py::class_<NativeScheduler>(m, "NativeScheduler")
         .def(py::init<int64_t, int64_t, int, int64_t, double, double, int,
                       int64_t, int64_t, double, int64_t, bool, double,

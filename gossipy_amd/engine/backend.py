@@ -1756,8 +1756,9 @@ class HIPBackend(TorchBackend):
         * the ops are ``tick_<name>`` and, for the families the whole-round
           executor admits, ``run_round_<name>``;
         * ``args`` is the family argument tuple both ops take after the data
-          arena (a tick op appends ``update_only``, a round op
-          ``rep_reply_slots``);
+          arena (a tick op appends ``update_only``); for plain logreg and
+          MLP it ends in ``merge_limit``, the limited-merge threshold or
+          ``-1`` without one;
         * ``chan`` names what rides the per-delivery channel: ``"pids"``
           (partition ids or sample seeds; tick ops take them after
           ``reply_slots``), ``"dmodes"`` (pass-through coins, the last tick
@@ -1806,10 +1807,8 @@ class HIPBackend(TorchBackend):
                 return "mlp_samp", (*shape, spec.samp_count(), *sgd), "pids"
             return "logreg_samp", (spec.samp_count(), *shape, *sgd), "pids"
         if fam in ("logreg", "mlp"):
-            if L is not None:
-                # the extension's second overload: merge_limit after mode
-                return fam, (*shape, *sgd, int(L)), "dmodes"
-            return fam, (*shape, *sgd), "dmodes"
+            # merge_limit after mode: -1 = plain mean merge
+            return fam, (*shape, *sgd, -1 if L is None else int(L)), "dmodes"
         if fam in ("pegasos", "adaline"):
             peg = fam == "pegasos"
             return (

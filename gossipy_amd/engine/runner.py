@@ -875,6 +875,18 @@ class BatchedGossipSimulator(SimulationEventSender):
                 )
         return out
 
+    @staticmethod
+    def _packed_path_on() -> bool:
+        """Whether the environment leaves the packed schedule in use: each
+        of these knobs routes a round around it."""
+        env = os.environ
+        return (
+            env.get("GOSSIPY_NO_MERGE") != "1"
+            and env.get("GOSSIPY_NO_PACK") != "1"
+            and env.get("GOSSIPY_COOP") != "1"
+            and not env.get("GOSSIPY_SB_MAX")
+        )
+
     def _maybe_merge(
         self, f: dict, pack: bool = True, force_py_pack: bool = False
     ) -> dict:
@@ -886,12 +898,7 @@ class BatchedGossipSimulator(SimulationEventSender):
         Tracks a cumulative (ticks, groups) counter for the perf probes."""
         if os.environ.get("GOSSIPY_NO_MERGE") == "1":
             return f
-        pack = (
-            pack
-            and os.environ.get("GOSSIPY_NO_PACK") != "1"
-            and os.environ.get("GOSSIPY_COOP") != "1"
-            and not os.environ.get("GOSSIPY_SB_MAX")
-        )
+        pack = pack and self._packed_path_on()
         packed = f.get("packed") if pack else None
         if packed is None and "recv_nodes" not in f:
             # lean flat: only the packed schedule was materialized — any
@@ -1196,68 +1203,30 @@ class BatchedGossipSimulator(SimulationEventSender):
         """Upload the round's flat event arrays in one H2D copy and hand
         the whole round to the C++ executor (ops/hip round executors)."""
         dev = self.device
-        dev_names = (
-            "snap_nodes",
-            "snap_slots",
-            "recv_nodes",
-            "recv_nptr",
-            "del_slots",
-            "reply_slots",
-            "pull_nodes",
-            "pull_slots",
-            "rep_nodes",
-            "rep_nptr",
-            "rep_slots",
-            "del_pids",
-            "rep_pids",
-            "rep_reply_slots",
-        )
+        ext = self.backend.ext
+        # the extension's table of a round's arrays (csrc/round_source.h):
+        # the upload lays them out in its order
         _empty = np.zeros(0, np.int32)
         parts = [
             np.ascontiguousarray(f.get(n, _empty), dtype=np.int32)
-            for n in dev_names
+            for n in ext.ROUND_ARRAY_NAMES
         ]
         lens = [len(p) for p in parts]
         host = np.concatenate(parts) if sum(lens) else np.zeros(1, np.int32)
         dbuf = torch.from_numpy(host).to(dev, non_blocking=True)
-        views = {}
-        off = 0
-        for n, l in zip(dev_names, lens):
-            views[n] = dbuf[off : off + l]
-            off += l
-        tp = {
-            n: torch.from_numpy(np.ascontiguousarray(f[n], dtype=np.int32))
-            for n in ("snap_tptr", "recv_tptr", "pull_tptr", "rep_tptr")
-        }
-        ext = self.backend.ext
+        tp = [
+            torch.from_numpy(np.ascontiguousarray(f[n], dtype=np.int32))
+            for n in ext.ROUND_TPTR_NAMES
+        ]
 
-        def leading(tptr):
-            # the block every run_round_* op starts with
-            return (
-                self.state.params,
-                self.state.ages,
-                self.pool.slots,
-                self.pool.slot_ages,
-                views["snap_nodes"],
-                views["snap_slots"],
-                tptr["snap_tptr"],
-                views["recv_nodes"],
-                views["recv_nptr"],
-                tptr["recv_tptr"],
-                views["del_slots"],
-                views["reply_slots"],
-                views["del_pids"],
-                views["pull_nodes"],
-                views["pull_slots"],
-                tptr["pull_tptr"],
-                views["rep_nodes"],
-                views["rep_nptr"],
-                tptr["rep_tptr"],
-                views["rep_slots"],
-                views["rep_pids"],
-                self.data.x,
-                self.data.y,
-                self.data.counts,
+        def call(op, tptr, *family):
+            # the block every run_round_* op starts with, then its own
+            op(
+                self.state.params, self.state.ages,
+                self.pool.slots, self.pool.slot_ages,
+                dbuf, lens, *tptr,
+                self.data.x, self.data.y, self.data.counts,
+                *family,
             )
 
         spec = self.spec
@@ -1275,14 +1244,15 @@ class BatchedGossipSimulator(SimulationEventSender):
             # ms/round at the flagship config: ~200 grid.sync barriers cost
             # more than ~200 stream launch gaps), so opt-in only
             # (GOSSIPY_COOP=1); kept as the measured alternative
-            per_tick = [
-                int(np.diff(f[n]).max()) for n in tp if len(f[n]) > 1
-            ]
+            per_tick = [int(np.diff(t).max()) for t in tp if len(t) > 1]
             max_batch = max(per_tick) if per_tick else 1
             try:
-                ext.run_round_coop_logreg(
-                    *leading({n: t.to(dev) for n, t in tp.items()}),
-                    *args,
+                # its tick pointers live on the device, and it takes no
+                # merge_limit (args' last, -1 here)
+                call(
+                    ext.run_round_coop_logreg,
+                    [t.to(dev) for t in tp],
+                    *args[:-1],
                     max_batch,
                 )
                 return
@@ -1291,9 +1261,7 @@ class BatchedGossipSimulator(SimulationEventSender):
                             "falling back to the stream executor", e)
                 self._coop_enabled = False
 
-        getattr(ext, "run_round_" + name)(
-            *leading(tp), *args, views["rep_reply_slots"]
-        )
+        call(getattr(ext, "run_round_" + name), tp, *args)
 
     #: ``False`` keeps the fast path's rounds on the Python round path even
     #: where the native round driver applies (see :meth:`_round_driver`)
@@ -1313,10 +1281,7 @@ class BatchedGossipSimulator(SimulationEventSender):
         if (
             fast
             and hasattr(self.scheduler, "set_lean")
-            and os.environ.get("GOSSIPY_NO_MERGE") != "1"
-            and os.environ.get("GOSSIPY_NO_PACK") != "1"
-            and os.environ.get("GOSSIPY_COOP") != "1"
-            and not os.environ.get("GOSSIPY_SB_MAX")
+            and self._packed_path_on()
         ):
             # fast path consumes only the packed schedule — skip the full
             # per-event array materialization and the multi-rank merge scan.
@@ -1468,10 +1433,7 @@ class BatchedGossipSimulator(SimulationEventSender):
             and self.use_round_driver
             and hasattr(self.scheduler, "round_source")
             and hasattr(self.scheduler, "set_lean")
-            and env.get("GOSSIPY_NO_MERGE") != "1"
-            and env.get("GOSSIPY_NO_PACK") != "1"
-            and env.get("GOSSIPY_COOP") != "1"
-            and not env.get("GOSSIPY_SB_MAX")
+            and self._packed_path_on()
             and self._exec_pool is None
             and self.world == 1
             and self.data.tx is None

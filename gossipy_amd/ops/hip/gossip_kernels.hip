@@ -42,6 +42,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_cooperative_groups.h>
 
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <deque>
@@ -49,6 +50,7 @@
 #include <string>
 #include <vector>
 
+#include "round_check.h"
 #include "round_layout.h"
 #include "round_ring.h"
 #include "round_source.h"
@@ -2838,34 +2840,20 @@ static void launch_tick(Plan<Args>& L, const TickEvents& ev, bool update_only,
     launch_kernel(L.kernel, n, L.threads, L.smem, current_stream(), L.a);
 }
 
-// The logreg and MLP entry points exist twice under one Python name: the
-// plain argument list, and one with `merge_limit` (the limited-merge
-// threshold L, -1 = off) directly after `mode`.
-void tick_logreg_lim(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
-                     torch::Tensor slot_ages, torch::Tensor nodes, torch::Tensor recv_ptr,
-                     torch::Tensor del_slots, torch::Tensor reply_slots,
-                     torch::Tensor X, torch::Tensor Y, torch::Tensor counts,
-                     int64_t d, int64_t k, double lr, double wd, int64_t epochs,
-                     int64_t bs, int64_t mode, int64_t merge_limit,
-                     bool update_only, torch::Tensor dmodes)
-{
-    auto L = logreg_plan({params, ages, slots, slot_ages, X, Y, counts},
-                         d, k, lr, wd, epochs, bs, mode, merge_limit);
-    launch_tick(L, {nodes, recv_ptr, del_slots, reply_slots}, update_only,
-                &LogregArgs::dmodes, dmodes);
-}
-
+// `merge_limit` of the logreg and MLP entry points is the limited-merge
+// threshold L, -1 = off.
 void tick_logreg(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
                  torch::Tensor slot_ages, torch::Tensor nodes, torch::Tensor recv_ptr,
                  torch::Tensor del_slots, torch::Tensor reply_slots,
                  torch::Tensor X, torch::Tensor Y, torch::Tensor counts,
                  int64_t d, int64_t k, double lr, double wd, int64_t epochs,
-                 int64_t bs, int64_t mode, bool update_only,
-                 torch::Tensor dmodes)
+                 int64_t bs, int64_t mode, int64_t merge_limit,
+                 bool update_only, torch::Tensor dmodes)
 {
-    tick_logreg_lim(params, ages, slots, slot_ages, nodes, recv_ptr, del_slots,
-                    reply_slots, X, Y, counts, d, k, lr, wd, epochs, bs, mode,
-                    -1, update_only, dmodes);
+    auto L = logreg_plan({params, ages, slots, slot_ages, X, Y, counts},
+                         d, k, lr, wd, epochs, bs, mode, merge_limit);
+    launch_tick(L, {nodes, recv_ptr, del_slots, reply_slots}, update_only,
+                &LogregArgs::dmodes, dmodes);
 }
 
 void tick_linear(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
@@ -2881,31 +2869,18 @@ void tick_linear(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
                 &LinearArgs::dmodes, dmodes);
 }
 
-void tick_mlp_lim(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
-                  torch::Tensor slot_ages, torch::Tensor nodes, torch::Tensor recv_ptr,
-                  torch::Tensor del_slots, torch::Tensor reply_slots,
-                  torch::Tensor X, torch::Tensor Y, torch::Tensor counts,
-                  torch::Tensor layout, int64_t n_layers, double lr, double wd,
-                  int64_t epochs, int64_t bs, int64_t mode, int64_t merge_limit,
-                  bool update_only, torch::Tensor dmodes)
-{
-    auto L = mlp_plan({params, ages, slots, slot_ages, X, Y, counts},
-                      layout, n_layers, lr, wd, epochs, bs, mode, merge_limit);
-    launch_tick(L, {nodes, recv_ptr, del_slots, reply_slots}, update_only,
-                &MlpArgs::dmodes, dmodes);
-}
-
 void tick_mlp(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
               torch::Tensor slot_ages, torch::Tensor nodes, torch::Tensor recv_ptr,
               torch::Tensor del_slots, torch::Tensor reply_slots,
               torch::Tensor X, torch::Tensor Y, torch::Tensor counts,
               torch::Tensor layout, int64_t n_layers, double lr, double wd,
-              int64_t epochs, int64_t bs, int64_t mode, bool update_only,
-              torch::Tensor dmodes)
+              int64_t epochs, int64_t bs, int64_t mode, int64_t merge_limit,
+              bool update_only, torch::Tensor dmodes)
 {
-    tick_mlp_lim(params, ages, slots, slot_ages, nodes, recv_ptr, del_slots,
-                 reply_slots, X, Y, counts, layout, n_layers, lr, wd, epochs,
-                 bs, mode, -1, update_only, dmodes);
+    auto L = mlp_plan({params, ages, slots, slot_ages, X, Y, counts},
+                      layout, n_layers, lr, wd, epochs, bs, mode, merge_limit);
+    launch_tick(L, {nodes, recv_ptr, del_slots, reply_slots}, update_only,
+                &MlpArgs::dmodes, dmodes);
 }
 
 void tick_logreg_part(
@@ -3004,67 +2979,33 @@ void tick_kmeans(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
 // ~200 launch enqueues of a few µs each.
 // ---------------------------------------------------------------------------
 
-// The leading parameters every run_round_* takes: the four state tensors,
-// the round's event arrays, then the data arena. del_pids / rep_pids carry
-// the partition ids (partitioned) or sample seeds (sampled) of each
-// delivery; the plain families ignore them.
-#define ROUND_PARAMS \
-    torch::Tensor params, torch::Tensor ages, torch::Tensor slots, \
-    torch::Tensor slot_ages, \
-    torch::Tensor snap_nodes, torch::Tensor snap_slots, torch::Tensor snap_tptr, \
-    torch::Tensor recv_nodes, torch::Tensor recv_nptr, torch::Tensor recv_tptr, \
-    torch::Tensor del_slots, torch::Tensor reply_slots, torch::Tensor del_pids, \
-    torch::Tensor pull_nodes, torch::Tensor pull_slots, torch::Tensor pull_tptr, \
-    torch::Tensor rep_nodes, torch::Tensor rep_nptr, torch::Tensor rep_tptr, \
-    torch::Tensor rep_slots, torch::Tensor rep_pids, \
-    torch::Tensor X, torch::Tensor Y, torch::Tensor counts
-#define ROUND_STATE {params, ages, slots, slot_ages, X, Y, counts}
-#define ROUND_EVENTS \
-    snap_nodes, snap_slots, snap_tptr, recv_nodes, recv_nptr, recv_tptr, \
-    del_slots, reply_slots, del_pids, pull_nodes, pull_slots, pull_tptr, \
-    rep_nodes, rep_nptr, rep_tptr, rep_slots, rep_pids
-
+// One round's arrays, indexed by the table of csrc/round_source.h.
+// del_pids / rep_pids carry the partition ids (partitioned) or sample seeds
+// (sampled) of each delivery; the plain families ignore them.
 struct RoundArrays {
-    // device pointers
-    const int *snap_nodes, *snap_slots;
-    const int *recv_nodes, *recv_nptr;
-    const int *del_slots, *reply_slots, *del_pids;
-    const int *pull_nodes, *pull_slots;
-    const int *rep_nodes, *rep_nptr, *rep_slots, *rep_pids, *rep_reply_slots;
+    const int* dev[ROUND_N_ARRAYS];  // device pointers; nullptr: empty
     // tick pointers [delta+1]: host-side for the stream executors,
-    // device-side for run_round_coop_logreg
-    const int *snap_tptr, *recv_tptr, *pull_tptr, *rep_tptr;
-    torch::Tensor tptr_tensors[4];  // the same four, for the upload
+    // device-side for the whole-round kernels
+    const int* tptr[ROUND_N_TPTRS];
     int delta;
 };
 
-static RoundArrays unpack_round(
-    torch::Tensor snap_nodes, torch::Tensor snap_slots, torch::Tensor snap_tptr,
-    torch::Tensor recv_nodes, torch::Tensor recv_nptr, torch::Tensor recv_tptr,
-    torch::Tensor del_slots, torch::Tensor reply_slots, torch::Tensor del_pids,
-    torch::Tensor pull_nodes, torch::Tensor pull_slots, torch::Tensor pull_tptr,
-    torch::Tensor rep_nodes, torch::Tensor rep_nptr, torch::Tensor rep_tptr,
-    torch::Tensor rep_slots, torch::Tensor rep_pids,
-    torch::Tensor rep_reply_slots)
+// The one place a RoundArrays is built: the arrays lie in one device buffer
+// at `base`, array i at off[i] with len[i] elements.
+static RoundArrays round_arrays(const int* base, const size_t* off,
+                                const size_t* len,
+                                const int* const tptr[ROUND_N_TPTRS],
+                                size_t tptr_len)
 {
     RoundArrays r;
-    r.snap_nodes = iptr(snap_nodes); r.snap_slots = iptr(snap_slots);
-    r.recv_nodes = iptr(recv_nodes); r.recv_nptr = recv_nptr.data_ptr<int>();
-    r.del_slots = iptr(del_slots); r.reply_slots = iptr(reply_slots);
-    r.del_pids = iptr(del_pids);
-    r.pull_nodes = iptr(pull_nodes); r.pull_slots = iptr(pull_slots);
-    r.rep_nodes = iptr(rep_nodes); r.rep_nptr = rep_nptr.data_ptr<int>();
-    r.rep_slots = iptr(rep_slots); r.rep_pids = iptr(rep_pids);
-    r.rep_reply_slots = iptr(rep_reply_slots);
-    r.snap_tptr = snap_tptr.data_ptr<int>();
-    r.recv_tptr = recv_tptr.data_ptr<int>();
-    r.pull_tptr = pull_tptr.data_ptr<int>();
-    r.rep_tptr = rep_tptr.data_ptr<int>();
-    r.tptr_tensors[0] = snap_tptr; r.tptr_tensors[1] = recv_tptr;
-    r.tptr_tensors[2] = pull_tptr; r.tptr_tensors[3] = rep_tptr;
-    r.delta = (int)snap_tptr.numel() - 1;
+    for (int i = 0; i < ROUND_N_ARRAYS; ++i)
+        r.dev[i] = len[i] ? base + off[i] : nullptr;
+    for (int i = 0; i < ROUND_N_TPTRS; ++i) r.tptr[i] = tptr[i];
+    r.delta = (int)tptr_len - 1;
     return r;
 }
+
+using TptrTensors = std::array<torch::Tensor, ROUND_N_TPTRS>;
 
 // The one stream round loop: per tick snapshot, deliver, pull-snapshot,
 // reply-deliver. `chan` names the family's per-delivery pids/seeds member
@@ -3085,19 +3026,22 @@ static void stream_round(Plan<Args>& L, const RoundArrays& r,
         if (chan) L.a.*chan = pids;
         launch_kernel(L.kernel, n, L.threads, L.smem, s, L.a);
     };
+    const int* const* a = r.dev;
     for (int t = 0; t < r.delta; ++t) {
-        int s0 = r.snap_tptr[t], s1 = r.snap_tptr[t + 1];
-        if (s1 > s0) snap(r.snap_nodes + s0, r.snap_slots + s0, s1 - s0);
-        int r0 = r.recv_tptr[t], r1 = r.recv_tptr[t + 1];
+        int s0 = r.tptr[RT_SNAP][t], s1 = r.tptr[RT_SNAP][t + 1];
+        if (s1 > s0)
+            snap(a[RA_SNAP_NODES] + s0, a[RA_SNAP_SLOTS] + s0, s1 - s0);
+        int r0 = r.tptr[RT_RECV][t], r1 = r.tptr[RT_RECV][t + 1];
         if (r1 > r0)
-            deliver(r.recv_nodes + r0, r.recv_nptr + r0, r1 - r0, r.del_slots,
-                    r.reply_slots, r.del_pids);
-        int p0 = r.pull_tptr[t], p1 = r.pull_tptr[t + 1];
-        if (p1 > p0) snap(r.pull_nodes + p0, r.pull_slots + p0, p1 - p0);
-        int q0 = r.rep_tptr[t], q1 = r.rep_tptr[t + 1];
+            deliver(a[RA_RECV_NODES] + r0, a[RA_RECV_NPTR] + r0, r1 - r0,
+                    a[RA_DEL_SLOTS], a[RA_REPLY_SLOTS], a[RA_DEL_PIDS]);
+        int p0 = r.tptr[RT_PULL][t], p1 = r.tptr[RT_PULL][t + 1];
+        if (p1 > p0)
+            snap(a[RA_PULL_NODES] + p0, a[RA_PULL_SLOTS] + p0, p1 - p0);
+        int q0 = r.tptr[RT_REP][t], q1 = r.tptr[RT_REP][t + 1];
         if (q1 > q0)
-            deliver(r.rep_nodes + q0, r.rep_nptr + q0, q1 - q0, r.rep_slots,
-                    r.rep_reply_slots, r.rep_pids);
+            deliver(a[RA_REP_NODES] + q0, a[RA_REP_NPTR] + q0, q1 - q0,
+                    a[RA_REP_SLOTS], a[RA_REP_REPLY_SLOTS], a[RA_REP_PIDS]);
     }
 }
 
@@ -3115,18 +3059,14 @@ static int sb_threshold()
 static int max_group(const RoundArrays& r)
 {
     int mx = 0;
-    for (int t = 0; t < r.delta; ++t) {
-        mx = std::max(mx, r.snap_tptr[t + 1] - r.snap_tptr[t]);
-        mx = std::max(mx, r.recv_tptr[t + 1] - r.recv_tptr[t]);
-        mx = std::max(mx, r.pull_tptr[t + 1] - r.pull_tptr[t]);
-        mx = std::max(mx, r.rep_tptr[t + 1] - r.rep_tptr[t]);
-    }
+    for (int t = 0; t < r.delta; ++t)
+        for (const int* p : r.tptr) mx = std::max(mx, p[t + 1] - p[t]);
     return mx;
 }
 
 static void set_pids(PartRoundArgs& c, const RoundArrays& r)
 {
-    c.del_pids = r.del_pids; c.rep_pids = r.rep_pids;
+    c.del_pids = r.dev[RA_DEL_PIDS]; c.rep_pids = r.dev[RA_REP_PIDS];
 }
 template <typename RoundArgs> static void set_pids(RoundArgs&, const RoundArrays&) {}
 
@@ -3134,22 +3074,20 @@ template <typename RoundArgs> static void set_pids(RoundArgs&, const RoundArrays
 // PartRoundArgs share their field names) from the plan's base args and the
 // round's arrays. The four tick pointers must be device-resident here.
 template <typename RoundArgs, typename Args>
-static RoundArgs round_args(const Args& base, const RoundArrays& r,
-                            const int* snap_tptr, const int* recv_tptr,
-                            const int* pull_tptr, const int* rep_tptr)
+static RoundArgs round_args(const Args& base, const RoundArrays& r)
 {
     RoundArgs c;
     c.base = base;
-    c.snap_nodes = r.snap_nodes; c.snap_slots = r.snap_slots;
-    c.snap_tptr = snap_tptr;
-    c.recv_nodes = r.recv_nodes; c.recv_nptr = r.recv_nptr;
-    c.recv_tptr = recv_tptr;
-    c.del_slots = r.del_slots; c.reply_slots = r.reply_slots;
-    c.pull_nodes = r.pull_nodes; c.pull_slots = r.pull_slots;
-    c.pull_tptr = pull_tptr;
-    c.rep_nodes = r.rep_nodes; c.rep_nptr = r.rep_nptr;
-    c.rep_tptr = rep_tptr;
-    c.rep_slots = r.rep_slots;
+    c.snap_nodes = r.dev[RA_SNAP_NODES]; c.snap_slots = r.dev[RA_SNAP_SLOTS];
+    c.snap_tptr = r.tptr[RT_SNAP];
+    c.recv_nodes = r.dev[RA_RECV_NODES]; c.recv_nptr = r.dev[RA_RECV_NPTR];
+    c.recv_tptr = r.tptr[RT_RECV];
+    c.del_slots = r.dev[RA_DEL_SLOTS]; c.reply_slots = r.dev[RA_REPLY_SLOTS];
+    c.pull_nodes = r.dev[RA_PULL_NODES]; c.pull_slots = r.dev[RA_PULL_SLOTS];
+    c.pull_tptr = r.tptr[RT_PULL];
+    c.rep_nodes = r.dev[RA_REP_NODES]; c.rep_nptr = r.dev[RA_REP_NPTR];
+    c.rep_tptr = r.tptr[RT_REP];
+    c.rep_slots = r.dev[RA_REP_SLOTS];
     set_pids(c, r);
     c.delta = r.delta;
     return c;
@@ -3157,159 +3095,188 @@ static RoundArgs round_args(const Args& base, const RoundArrays& r,
 
 // Single-workgroup fallback for tiny batches: the family's whole-round
 // kernel launched PLAIN with one workgroup (in the coop kernel round_sync
-// degrades to __syncthreads) — one launch for the round. Returns false,
-// having done nothing, when the round does not qualify.
+// degrades to __syncthreads) — one launch for the round. `tptr` are the
+// host tensors behind r.tptr; the kernel reads copies of them on `dev`.
+// Returns false, having done nothing, when the round does not qualify.
 template <typename RoundArgs, typename Args>
 static bool single_block_round(void (*kernel)(RoundArgs), const Plan<Args>& L,
-                               const RoundArrays& r, torch::Device dev)
+                               const RoundArrays& r, const TptrTensors& tptr,
+                               torch::Device dev)
 {
-    if (!(max_group(r) <= sb_threshold() && r.rep_reply_slots == nullptr))
+    if (!(max_group(r) <= sb_threshold() &&
+          r.dev[RA_REP_REPLY_SLOTS] == nullptr))
         return false;
-    torch::Tensor t[4];
-    for (int i = 0; i < 4; ++i) t[i] = r.tptr_tensors[i].to(dev);
-    RoundArgs c = round_args<RoundArgs>(
-        L.a, r, t[0].data_ptr<int>(), t[1].data_ptr<int>(),
-        t[2].data_ptr<int>(), t[3].data_ptr<int>());
+    TptrTensors t;
+    RoundArrays on_dev = r;
+    for (int i = 0; i < ROUND_N_TPTRS; ++i) {
+        t[i] = tptr[i].to(dev);
+        on_dev.tptr[i] = t[i].data_ptr<int>();
+    }
+    RoundArgs c = round_args<RoundArgs>(L.a, on_dev);
     launch_kernel(kernel, 1, L.threads, L.smem, current_stream(), c);
     // keep the uploaded tptr tensors alive past the async launch
     static thread_local std::vector<torch::Tensor> keep;
-    keep.insert(keep.end(), t, t + 4);
+    keep.insert(keep.end(), t.begin(), t.end());
     if (keep.size() > 64) keep.erase(keep.begin(), keep.begin() + 32);
     return true;
 }
 
-void run_round_logreg_lim(
-    ROUND_PARAMS,
-    int64_t d, int64_t k, double lr, double wd, int64_t epochs, int64_t bs,
-    int64_t mode, int64_t merge_limit, torch::Tensor rep_reply_slots)
+// What a run_round_* body works on: round_entry (below) makes it from the
+// leading parameters every run_round_* op takes,
+//   params, ages, slots, slot_ages,
+//   round_buf  int32 [*] on the device: the arrays in table order
+//   lens       their ROUND_N_ARRAYS lengths
+//   snap_tptr, recv_tptr, pull_tptr, rep_tptr  int32 [n_groups + 1]
+//   X, Y, counts
+// and the family's own arguments follow.
+struct RoundCall {
+    StateTensors st;
+    RoundArrays r;
+    TptrTensors tptr;  // the tensors behind r.tptr
+};
+
+// Binds `body` as a run_round_* op. The round is validated before any
+// pointer is formed; a bad one raises and launches nothing. The tick
+// pointers are read on the host by the stream executors and on the device by
+// the cooperative kernel, so `tptr_on_dev` says where they must live.
+template <typename... Family>
+static auto round_entry(void (*body)(const RoundCall&, Family...),
+                        bool tptr_on_dev = false)
 {
-    auto L = logreg_plan(ROUND_STATE, d, k, lr, wd, epochs, bs, mode,
-                         merge_limit);
-    RoundArrays r = unpack_round(ROUND_EVENTS, rep_reply_slots);
+    return [body, tptr_on_dev](
+               torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
+               torch::Tensor slot_ages, torch::Tensor round_buf,
+               std::vector<int64_t> lens, torch::Tensor snap_tptr,
+               torch::Tensor recv_tptr, torch::Tensor pull_tptr,
+               torch::Tensor rep_tptr, torch::Tensor X, torch::Tensor Y,
+               torch::Tensor counts, Family... family) {
+        TORCH_CHECK(round_buf.is_cuda() && round_buf.is_contiguous() &&
+                        round_buf.scalar_type() == torch::kInt32 &&
+                        round_buf.dim() == 1,
+                    "round_buf must be contiguous int32 [*] on device");
+        TORCH_CHECK(lens.size() == (size_t)ROUND_N_ARRAYS, "lens must have ",
+                    (int)ROUND_N_ARRAYS, " entries, got ", lens.size());
+        size_t off[ROUND_N_ARRAYS], len[ROUND_N_ARRAYS], total = 0;
+        const size_t room = (size_t)round_buf.numel();
+        for (int i = 0; i < ROUND_N_ARRAYS; ++i) {
+            // each length against the room left: the sum cannot wrap
+            TORCH_CHECK(lens[i] >= 0 && (size_t)lens[i] <= room - total,
+                        "lens[", i, "] (", ROUND_ARRAY_NAMES[i], ") = ",
+                        lens[i], " is negative or runs past round_buf");
+            off[i] = total;
+            len[i] = (size_t)lens[i];
+            total += len[i];
+        }
+        RoundCall c{{params, ages, slots, slot_ages, X, Y, counts},
+                    {},
+                    {snap_tptr, recv_tptr, pull_tptr, rep_tptr}};
+        const int* tp[ROUND_N_TPTRS];
+        for (int i = 0; i < ROUND_N_TPTRS; ++i) {
+            const torch::Tensor& t = c.tptr[i];
+            TORCH_CHECK(t.is_cuda() == tptr_on_dev && t.is_contiguous() &&
+                            t.scalar_type() == torch::kInt32 &&
+                            t.numel() >= 1 &&
+                            t.numel() == c.tptr[0].numel(),
+                        ROUND_TPTR_NAMES[i], " must be contiguous int32 on ",
+                        tptr_on_dev ? "device" : "host",
+                        ", non-empty and as long as ", ROUND_TPTR_NAMES[0]);
+            tp[i] = t.data_ptr<int>();
+        }
+        c.r = round_arrays(round_buf.data_ptr<int>(), off, len, tp,
+                           (size_t)snap_tptr.numel());
+        body(c, family...);
+    };
+}
+
+static void run_round_logreg(
+    const RoundCall& c, int64_t d, int64_t k, double lr, double wd,
+    int64_t epochs, int64_t bs, int64_t mode, int64_t merge_limit)
+{
+    auto L = logreg_plan(c.st, d, k, lr, wd, epochs, bs, mode, merge_limit);
     // the single-workgroup round kernel has no limited-merge instantiation
     if (merge_limit < 0 &&
-        single_block_round(coop_round_logreg_kernel, L, r, params.device()))
+        single_block_round(coop_round_logreg_kernel, L, c.r, c.tptr,
+                           c.st.params.device()))
         return;
-    stream_round(L, r);
+    stream_round(L, c.r);
 }
 
-void run_round_logreg(
-    ROUND_PARAMS,
-    int64_t d, int64_t k, double lr, double wd, int64_t epochs, int64_t bs,
-    int64_t mode, torch::Tensor rep_reply_slots)
+static void run_round_linear(const RoundCall& c, int64_t d, double lrlam,
+                             int64_t is_pegasos, int64_t mode)
 {
-    run_round_logreg_lim(params, ages, slots, slot_ages, ROUND_EVENTS, X, Y,
-                         counts, d, k, lr, wd, epochs, bs, mode, -1,
-                         rep_reply_slots);
-}
-
-void run_round_linear(
-    ROUND_PARAMS,
-    int64_t d, double lrlam, int64_t is_pegasos, int64_t mode,
-    torch::Tensor rep_reply_slots)
-{
-    auto L = linear_plan(ROUND_STATE, d, lrlam, is_pegasos, mode);
-    RoundArrays r = unpack_round(ROUND_EVENTS, rep_reply_slots);
-    if (single_block_round(sb_round_linear_kernel, L, r, params.device()))
+    auto L = linear_plan(c.st, d, lrlam, is_pegasos, mode);
+    if (single_block_round(sb_round_linear_kernel, L, c.r, c.tptr,
+                           c.st.params.device()))
         return;
-    stream_round(L, r);
+    stream_round(L, c.r);
 }
 
-void run_round_logreg_part(
-    ROUND_PARAMS,
-    torch::Tensor perm, torch::Tensor pptr, torch::Tensor apart,
-    int64_t n_parts, int64_t d, int64_t k, double lr, double wd,
-    int64_t epochs, int64_t bs, int64_t mode, torch::Tensor rep_reply_slots)
+static void run_round_logreg_part(
+    const RoundCall& c, torch::Tensor perm, torch::Tensor pptr,
+    torch::Tensor apart, int64_t n_parts, int64_t d, int64_t k, double lr,
+    double wd, int64_t epochs, int64_t bs, int64_t mode)
 {
-    auto L = logreg_part_plan(ROUND_STATE, perm, pptr, apart, n_parts, d, k,
-                              lr, wd, epochs, bs, mode);
-    RoundArrays r = unpack_round(ROUND_EVENTS, rep_reply_slots);
-    if (single_block_round(sb_round_logreg_part_kernel, L, r, params.device()))
+    auto L = logreg_part_plan(c.st, perm, pptr, apart, n_parts, d, k, lr, wd,
+                              epochs, bs, mode);
+    if (single_block_round(sb_round_logreg_part_kernel, L, c.r, c.tptr,
+                           c.st.params.device()))
         return;
-    stream_round(L, r, &LogregPartArgs::dpids);
+    stream_round(L, c.r, &LogregPartArgs::dpids);
 }
 
-void run_round_logreg_samp(
-    ROUND_PARAMS,
-    int64_t samp_c, int64_t d, int64_t k, double lr, double wd,
-    int64_t epochs, int64_t bs, int64_t mode, torch::Tensor rep_reply_slots)
+static void run_round_logreg_samp(
+    const RoundCall& c, int64_t samp_c, int64_t d, int64_t k, double lr,
+    double wd, int64_t epochs, int64_t bs, int64_t mode)
 {
-    auto L = logreg_samp_plan(ROUND_STATE, samp_c, d, k, lr, wd, epochs, bs,
-                              mode);
-    RoundArrays r = unpack_round(ROUND_EVENTS, rep_reply_slots);
-    stream_round(L, r, &LogregSampArgs::dseeds);
+    auto L = logreg_samp_plan(c.st, samp_c, d, k, lr, wd, epochs, bs, mode);
+    stream_round(L, c.r, &LogregSampArgs::dseeds);
 }
 
-void run_round_mlp_lim(
-    ROUND_PARAMS,
-    torch::Tensor layout, int64_t n_layers, double lr, double wd,
-    int64_t epochs, int64_t bs, int64_t mode, int64_t merge_limit,
-    torch::Tensor rep_reply_slots)
+static void run_round_mlp(
+    const RoundCall& c, torch::Tensor layout, int64_t n_layers, double lr,
+    double wd, int64_t epochs, int64_t bs, int64_t mode, int64_t merge_limit)
 {
-    auto L = mlp_plan(ROUND_STATE, layout, n_layers, lr, wd, epochs, bs, mode,
+    auto L = mlp_plan(c.st, layout, n_layers, lr, wd, epochs, bs, mode,
                       merge_limit);
-    RoundArrays r = unpack_round(ROUND_EVENTS, rep_reply_slots);
-    stream_round(L, r);
+    stream_round(L, c.r);
 }
 
-void run_round_mlp(
-    ROUND_PARAMS,
-    torch::Tensor layout, int64_t n_layers, double lr, double wd,
-    int64_t epochs, int64_t bs, int64_t mode, torch::Tensor rep_reply_slots)
-{
-    run_round_mlp_lim(params, ages, slots, slot_ages, ROUND_EVENTS, X, Y,
-                      counts, layout, n_layers, lr, wd, epochs, bs, mode, -1,
-                      rep_reply_slots);
-}
-
-void run_round_mlp_part(
-    ROUND_PARAMS,
-    torch::Tensor layout, int64_t n_layers,
+static void run_round_mlp_part(
+    const RoundCall& c, torch::Tensor layout, int64_t n_layers,
     torch::Tensor perm, torch::Tensor pptr, torch::Tensor apart,
     int64_t n_parts, double lr, double wd, int64_t epochs, int64_t bs,
-    int64_t mode, torch::Tensor rep_reply_slots)
+    int64_t mode)
 {
-    auto L = mlp_comp_plan(true, ROUND_STATE, layout, n_layers, perm, pptr,
-                           apart, n_parts, 0, lr, wd, epochs, bs, mode);
-    RoundArrays r = unpack_round(ROUND_EVENTS, rep_reply_slots);
-    stream_round(L, r, &MlpCompArgs::dpids);
+    auto L = mlp_comp_plan(true, c.st, layout, n_layers, perm, pptr, apart,
+                           n_parts, 0, lr, wd, epochs, bs, mode);
+    stream_round(L, c.r, &MlpCompArgs::dpids);
 }
 
-void run_round_mlp_samp(
-    ROUND_PARAMS,
-    torch::Tensor layout, int64_t n_layers, int64_t samp_c,
-    double lr, double wd, int64_t epochs, int64_t bs, int64_t mode,
-    torch::Tensor rep_reply_slots)
+static void run_round_mlp_samp(
+    const RoundCall& c, torch::Tensor layout, int64_t n_layers,
+    int64_t samp_c, double lr, double wd, int64_t epochs, int64_t bs,
+    int64_t mode)
 {
-    auto L = mlp_comp_plan(false, ROUND_STATE, layout, n_layers, {}, {}, {},
-                           0, samp_c, lr, wd, epochs, bs, mode);
-    RoundArrays r = unpack_round(ROUND_EVENTS, rep_reply_slots);
-    stream_round(L, r, &MlpCompArgs::dpids);
+    auto L = mlp_comp_plan(false, c.st, layout, n_layers, {}, {}, {}, 0,
+                           samp_c, lr, wd, epochs, bs, mode);
+    stream_round(L, c.r, &MlpCompArgs::dpids);
 }
 
-void run_round_mf(
-    ROUND_PARAMS,
-    int64_t k, int64_t n_items, double reg, double lr,
-    torch::Tensor rep_reply_slots)
+static void run_round_mf(const RoundCall& c, int64_t k, int64_t n_items,
+                         double reg, double lr)
 {
-    auto L = mf_plan(ROUND_STATE, k, n_items, reg, lr);
-    RoundArrays r = unpack_round(ROUND_EVENTS, rep_reply_slots);
-    stream_round(L, r);
+    auto L = mf_plan(c.st, k, n_items, reg, lr);
+    stream_round(L, c.r);
 }
 
-void run_round_coop_logreg(
-    ROUND_PARAMS,
-    int64_t d, int64_t k, double lr, double wd, int64_t epochs, int64_t bs,
-    int64_t mode, int64_t max_batch)
+// NOTE: unlike the stream executors, ALL arrays (tick ptrs included) are
+// device-resident here (bound with tptr_on_dev).
+static void run_round_coop_logreg(
+    const RoundCall& rc, int64_t d, int64_t k, double lr, double wd,
+    int64_t epochs, int64_t bs, int64_t mode, int64_t max_batch)
 {
-    // NOTE: unlike the stream executor, ALL arrays (tick ptrs included)
-    // must be device-resident here.
-    CHECK_DEV(snap_tptr); CHECK_DEV(recv_tptr); CHECK_DEV(pull_tptr);
-    CHECK_DEV(rep_tptr);
-    auto L = logreg_plan(ROUND_STATE, d, k, lr, wd, epochs, bs, mode);
-    RoundArrays r = unpack_round(ROUND_EVENTS, torch::Tensor());
-    CoopRoundArgs c = round_args<CoopRoundArgs>(
-        L.a, r, r.snap_tptr, r.recv_tptr, r.pull_tptr, r.rep_tptr);
+    auto L = logreg_plan(rc.st, d, k, lr, wd, epochs, bs, mode);
+    CoopRoundArgs c = round_args<CoopRoundArgs>(L.a, rc.r);
     int grid = std::max<int>(1, (int)max_batch);
     // stay within guaranteed cooperative residency
     int max_blocks = 0;
@@ -3534,15 +3501,14 @@ public:
         src_ = *static_cast<const RoundSource*>(source.get_pointer());
         CHECK_DEV(gx); CHECK_DEV(gy);
         if (family == "logreg") {
-            TORCH_CHECK(plan.size() == 7 || plan.size() == 8,
-                        "logreg plan: (d, k, lr, wd, epochs, bs, mode"
-                        "[, merge_limit])");
+            TORCH_CHECK(plan.size() == 8,
+                        "logreg plan: (d, k, lr, wd, epochs, bs, mode,"
+                        " merge_limit)");
             lg_ = logreg_plan(
                 st_, plan[0].cast<int64_t>(), plan[1].cast<int64_t>(),
                 plan[2].cast<double>(), plan[3].cast<double>(),
                 plan[4].cast<int64_t>(), plan[5].cast<int64_t>(),
-                plan[6].cast<int64_t>(),
-                plan.size() == 8 ? plan[7].cast<int64_t>() : -1);
+                plan[6].cast<int64_t>(), plan[7].cast<int64_t>());
             ev_.d = lg_.a.d; ev_.k = lg_.a.k; ev_.is_margin = 0;
         } else if (family == "linear") {
             TORCH_CHECK(plan.size() == 4,
@@ -3812,7 +3778,12 @@ private:
             RoundLayout lay;
             if (!write_round_layout(v, 0, sl.h, sl.cap, &lay))
                 throw std::runtime_error("RoundDriver: upload slot too small");
-            check_bounds(v, lay, sl.h);
+            // a schedule that fails this is never uploaded
+            if (const char* what = round_bounds_error(v.tptr, lay, sl.h,
+                                                      n_local_, pool_cap_))
+                throw std::runtime_error(
+                    std::string("RoundDriver: schedule out of bounds: ") +
+                    what);
             if (side_upload_) {
                 // the copy may not overtake the compute stream's reads of
                 // this device buffer four rounds ago: the slot's event has
@@ -3828,23 +3799,10 @@ private:
                                         hipMemcpyHostToDevice, s));
             }
 
-            RoundArrays ra;
-            auto dp = [&](int id) -> const int* {
-                return lay.len[id] ? sl.d + lay.off[id] : nullptr;
-            };
-            ra.snap_nodes = dp(RA_SNAP_NODES); ra.snap_slots = dp(RA_SNAP_SLOTS);
-            ra.recv_nodes = dp(RA_RECV_NODES); ra.recv_nptr = dp(RA_RECV_NPTR);
-            ra.del_slots = dp(RA_DEL_SLOTS); ra.reply_slots = dp(RA_REPLY_SLOTS);
-            ra.del_pids = dp(RA_DEL_PIDS);
-            ra.pull_nodes = dp(RA_PULL_NODES); ra.pull_slots = dp(RA_PULL_SLOTS);
-            ra.rep_nodes = dp(RA_REP_NODES); ra.rep_nptr = dp(RA_REP_NPTR);
-            ra.rep_slots = dp(RA_REP_SLOTS); ra.rep_pids = dp(RA_REP_PIDS);
-            ra.rep_reply_slots = dp(RA_REP_REPLY_SLOTS);
-            ra.snap_tptr = v.tptr[RT_SNAP].data;
-            ra.recv_tptr = v.tptr[RT_RECV].data;
-            ra.pull_tptr = v.tptr[RT_PULL].data;
-            ra.rep_tptr = v.tptr[RT_REP].data;
-            ra.delta = (int)v.tptr[RT_SNAP].len - 1;
+            const int* tp[ROUND_N_TPTRS];
+            for (int i = 0; i < ROUND_N_TPTRS; ++i) tp[i] = v.tptr[i].data;
+            RoundArrays ra = round_arrays(sl.d, lay.off, lay.len, tp,
+                                          v.tptr[RT_SNAP].len);
             last_groups_ = ra.delta;
             if (linear_) stream_round(ln_, ra); else stream_round(lg_, ra);
             RD_CHECK(hipGetLastError());
@@ -3891,71 +3849,6 @@ private:
             }
             throw;
         }
-    }
-
-    // Every index the kernels will follow stays inside its array: node ids
-    // below n_local, slot ids below the pool capacity (a negative reply slot
-    // means "none" to the kernels), CSR pointers and tick
-    // pointers monotone and inside their targets. One pass over a few KB of
-    // host memory; a schedule that fails it is never uploaded.
-    void check_bounds(const RoundView& v, const RoundLayout& lay,
-                      const int32_t* h) const
-    {
-        auto bad = [](const char* what) {
-            throw std::runtime_error(
-                std::string("RoundDriver: schedule out of bounds: ") + what);
-        };
-        auto all_in = [&](int id, int64_t lo, int64_t hi, const char* what) {
-            const int32_t* p = h + lay.off[id];
-            for (size_t i = 0; i < lay.len[id]; ++i)
-                if (p[i] < lo || p[i] >= hi) bad(what);
-        };
-        auto csr = [&](int id, size_t target, const char* what) {
-            const int32_t* p = h + lay.off[id];
-            if (lay.len[id] == 0 || p[0] != 0) bad(what);
-            for (size_t i = 1; i < lay.len[id]; ++i)
-                if (p[i] < p[i - 1]) bad(what);
-            if ((size_t)p[lay.len[id] - 1] > target) bad(what);
-        };
-        auto tptr = [&](int id, size_t target, size_t groups,
-                        const char* what) {
-            const RoundSpan& t = v.tptr[id];
-            if (t.len != groups + 1 || t.data[0] != 0) bad(what);
-            for (size_t i = 1; i < t.len; ++i)
-                if (t.data[i] < t.data[i - 1]) bad(what);
-            if ((size_t)t.data[t.len - 1] > target) bad(what);
-        };
-        if (v.tptr[RT_SNAP].len < 1) bad("snap_tptr");
-        size_t groups = v.tptr[RT_SNAP].len - 1;
-        all_in(RA_SNAP_NODES, 0, n_local_, "snap_nodes");
-        all_in(RA_SNAP_SLOTS, 0, pool_cap_, "snap_slots");
-        if (lay.len[RA_SNAP_SLOTS] != lay.len[RA_SNAP_NODES]) bad("snap_slots");
-        all_in(RA_RECV_NODES, 0, n_local_, "recv_nodes");
-        all_in(RA_DEL_SLOTS, 0, pool_cap_, "del_slots");
-        all_in(RA_REPLY_SLOTS, INT32_MIN, pool_cap_, "reply_slots");
-        all_in(RA_REP_NODES, 0, n_local_, "rep_nodes");
-        all_in(RA_REP_SLOTS, 0, pool_cap_, "rep_slots");
-        all_in(RA_REP_REPLY_SLOTS, INT32_MIN, pool_cap_, "rep_reply_slots");
-        if (lay.len[RA_PULL_NODES] || lay.len[RA_PULL_SLOTS])
-            bad("pull arrays in a packed round");
-        if (lay.len[RA_RECV_NPTR] != lay.len[RA_RECV_NODES] + 1) bad("recv_nptr");
-        if (lay.len[RA_REP_NPTR] != lay.len[RA_REP_NODES] + 1) bad("rep_nptr");
-        csr(RA_RECV_NPTR, lay.len[RA_DEL_SLOTS], "recv_nptr");
-        csr(RA_REP_NPTR, lay.len[RA_REP_SLOTS], "rep_nptr");
-        auto same_or_empty = [&](int id, int as, const char* what) {
-            if (lay.len[id] && lay.len[id] != lay.len[as]) bad(what);
-        };
-        same_or_empty(RA_REPLY_SLOTS, RA_DEL_SLOTS, "reply_slots");
-        same_or_empty(RA_DEL_PIDS, RA_DEL_SLOTS, "del_pids");
-        same_or_empty(RA_REP_REPLY_SLOTS, RA_REP_SLOTS, "rep_reply_slots");
-        same_or_empty(RA_REP_PIDS, RA_REP_SLOTS, "rep_pids");
-        tptr(RT_SNAP, lay.len[RA_SNAP_NODES], groups, "snap_tptr");
-        tptr(RT_RECV, lay.len[RA_RECV_NODES], groups, "recv_tptr");
-        tptr(RT_PULL, 0, groups, "pull_tptr");
-        tptr(RT_REP, lay.len[RA_REP_NODES], groups, "rep_tptr");
-        const int32_t* ids = h + lay.eval_off;
-        for (size_t i = 0; i < lay.n_eval; ++i)
-            if (ids[i] < 0 || ids[i] >= n_local_) bad("eval ids");
     }
 
     void release() noexcept
@@ -4035,25 +3928,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           "(pinned host buffers, device buffers, events, streams) held by "
           "the RoundDrivers of this process");
     m.def("snapshot", &snapshot, "batched model snapshot (arena row copy)");
-    m.def("tick_logreg", &tick_logreg, "fused merge + logreg SGD tick");
-    m.def("tick_logreg", &tick_logreg_lim,
+    // the table of round_source.h: the order of round_buf and lens
+    py::tuple arrays((size_t)ROUND_N_ARRAYS), tptrs((size_t)ROUND_N_TPTRS);
+    for (int i = 0; i < ROUND_N_ARRAYS; ++i) arrays[i] = ROUND_ARRAY_NAMES[i];
+    for (int i = 0; i < ROUND_N_TPTRS; ++i) tptrs[i] = ROUND_TPTR_NAMES[i];
+    m.attr("ROUND_ARRAY_NAMES") = arrays;
+    m.attr("ROUND_TPTR_NAMES") = tptrs;
+    m.def("tick_logreg", &tick_logreg,
           "fused merge + logreg SGD tick, merge_limit after mode");
     m.def("tick_linear", &tick_linear, "fused merge + pegasos/adaline tick");
-    m.def("tick_mlp", &tick_mlp, "fused merge + MLP SGD tick");
-    m.def("tick_mlp", &tick_mlp_lim,
+    m.def("tick_mlp", &tick_mlp,
           "fused merge + MLP SGD tick, merge_limit after mode");
-    m.def("run_round_logreg", &run_round_logreg,
-          "whole-round executor, logreg family",
-          py::call_guard<py::gil_scoped_release>());
-    m.def("run_round_logreg", &run_round_logreg_lim,
+    m.def("run_round_logreg", round_entry(run_round_logreg),
           "whole-round executor, logreg family, merge_limit after mode",
           py::call_guard<py::gil_scoped_release>());
-    m.def("run_round_linear", &run_round_linear,
+    m.def("run_round_linear", round_entry(run_round_linear),
           "whole-round executor, pegasos/adaline family",
           py::call_guard<py::gil_scoped_release>());
     m.def("tick_logreg_part", &tick_logreg_part,
           "fused partition-merge + age-rescaled logreg SGD tick (K7/K8)");
-    m.def("run_round_logreg_part", &run_round_logreg_part,
+    m.def("run_round_logreg_part", round_entry(run_round_logreg_part),
           "whole-round executor, partitioned logreg family",
           py::call_guard<py::gil_scoped_release>());
     m.def("wmerge", &wmerge, "all2all weighted k-way merge (K5 weighted)");
@@ -4061,29 +3955,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           "fused sampled-merge + logreg SGD tick (K6)");
     m.def("tick_mf", &tick_mf,
           "fused item-block merge + per-rating MF SGD tick (K9/K10)");
-    m.def("run_round_mlp", &run_round_mlp,
-          "whole-round executor, MLP family",
-          py::call_guard<py::gil_scoped_release>());
-    m.def("run_round_mlp", &run_round_mlp_lim,
+    m.def("run_round_mlp", round_entry(run_round_mlp),
           "whole-round executor, MLP family, merge_limit after mode",
           py::call_guard<py::gil_scoped_release>());
     m.def("tick_mlp_part", &tick_mlp_part,
           "fused partition-merge + age-rescaled MLP SGD tick");
     m.def("tick_mlp_samp", &tick_mlp_samp,
           "fused sampled-merge + MLP SGD tick");
-    m.def("run_round_mlp_part", &run_round_mlp_part,
+    m.def("run_round_mlp_part", round_entry(run_round_mlp_part),
           "whole-round executor, partitioned MLP family",
           py::call_guard<py::gil_scoped_release>());
-    m.def("run_round_mlp_samp", &run_round_mlp_samp,
+    m.def("run_round_mlp_samp", round_entry(run_round_mlp_samp),
           "whole-round executor, sampled MLP family",
           py::call_guard<py::gil_scoped_release>());
-    m.def("run_round_logreg_samp", &run_round_logreg_samp,
+    m.def("run_round_logreg_samp", round_entry(run_round_logreg_samp),
           "whole-round executor, sampled logreg family",
           py::call_guard<py::gil_scoped_release>());
-    m.def("run_round_mf", &run_round_mf,
+    m.def("run_round_mf", round_entry(run_round_mf),
           "whole-round executor, MF recommender family",
           py::call_guard<py::gil_scoped_release>());
-    m.def("run_round_coop_logreg", &run_round_coop_logreg,
+    m.def("run_round_coop_logreg", round_entry(run_round_coop_logreg, true),
           "single-launch cooperative whole-round executor (logreg)");
     m.def("tick_pens", &tick_pens,
           "PENS step-1 event: score candidates, merge top-m, count winners");

@@ -2212,6 +2212,16 @@ class TestFamilyCall:
                 else None if name == "mf" else "dmodes"
             )
             names.add(name)
+            if name in ("logreg", "mlp"):
+                # merge_limit is always passed: -1 without a threshold
+                assert args[-1] == -1 and type(args[-1]) is int
+                spec.age_diff_threshold = 3
+                lim_name, lim_args, _ = hip._family_call(spec, CPU)
+                assert lim_name == name
+                assert lim_args[-1] == 3 and type(lim_args[-1]) is int
+                assert len(lim_args) == len(args)
+                for a, b in zip(lim_args[:-1], args[:-1]):
+                    assert a is b or a == b
         name, _, chan = hip._family_call(AdaLineSpec(d_in=5), CPU)
         assert (name, chan) == ("linear", "dmodes")
         # every stream round executor of the extension is reachable

@@ -1147,7 +1147,7 @@ class TestRoundExecutorGuards:
         i32 = dict(dtype=torch.int32, device=CUDA)
         sgd = (0.1, 0.0, 1, 0, 1)
         if name == "logreg":
-            return 57 * v + v, 57, (57, v, *sgd)
+            return 57 * v + v, 57, (57, v, *sgd, -1)  # merge_limit: off
         if name == "logreg_part":
             D = 57 * v + v
             perm = torch.arange(D, **i32)
@@ -1188,9 +1188,11 @@ class TestRoundExecutorGuards:
                 *state, e, e, e, e, *pids, *arena, *args, False, *dmodes
             ),
             lambda: getattr(ext, "run_round_" + name)(
-                *state, e, e, tptr, e, e, tptr, e, e, e, e, e, tptr, e, e,
-                tptr, e, e, *arena, *args,
+                *state,
+                # the upload: every array empty but the last, rep_reply_slots
                 torch.zeros(1, dtype=torch.int32, device=CUDA),
+                [0] * (len(ext.ROUND_ARRAY_NAMES) - 1) + [1],
+                tptr, tptr, tptr, tptr, *arena, *args,
             ),
         )
         for call in calls:

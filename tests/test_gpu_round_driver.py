@@ -260,6 +260,100 @@ def test_set_pool_rejects_a_pool_the_plan_cannot_write(monkeypatch):
     assert a.rounds_done == 2
 
 
+def _tiny_round():
+    """8 nodes, a pool of 8 slots, one group: node 2 snapshots into slot 3,
+    node 5 receives it. Returns a fresh simulator and the round's flat
+    dict."""
+    import numpy as np
+
+    n = 8
+    g = torch.Generator().manual_seed(4)
+    shards = [
+        (torch.randn(3 + i % 4, D_IN, generator=g),
+         torch.randint(0, 2, (3 + i % 4,), generator=g).float())
+        for i in range(n)
+    ]
+    spec = _spec()
+    cfg = EngineConfig(n_nodes=n, delta=4, model_size=spec.D, seed=5,
+                       protocol=AntiEntropyProtocol.PUSH)
+    sim = BatchedGossipSimulator(
+        cfg, spec, DataArena.from_shards(shards, CUDA), device=CUDA)
+    sim.init_nodes(seed=3)
+    sim.pool = SlotPool(spec.D, CUDA, capacity=8)
+    i32 = lambda *v: np.array(v, np.int32)
+    flat = {
+        "snap_nodes": i32(2), "snap_slots": i32(3), "snap_tptr": i32(0, 1),
+        "recv_nodes": i32(5), "recv_nptr": i32(0, 1), "recv_tptr": i32(0, 1),
+        "del_slots": i32(3), "reply_slots": i32(-1),
+        "pull_tptr": i32(0, 0), "rep_nptr": i32(0), "rep_tptr": i32(0, 0),
+    }
+    return sim, flat
+
+
+def test_run_round_takes_the_upload_and_refuses_a_bad_one():
+    """``run_round_*`` take the one upload buffer, its lengths and the four
+    tick pointers. A direct call leaves what ``_run_round_fast`` leaves from
+    the same flat dict; a buffer, lengths or tick pointers that do not fit
+    together raise before anything is launched."""
+    import numpy as np
+
+    from gossipy_amd import ops
+
+    ext = ops.load_extension()
+    a, flat = _tiny_round()
+    b, _ = _tiny_round()
+    start = b.state.params.clone()
+    a._run_round_fast(flat)
+
+    empty = np.zeros(0, np.int32)
+    parts = [flat.get(n, empty) for n in ext.ROUND_ARRAY_NAMES]
+    lens = [len(p) for p in parts]
+    assert sum(lens) == 8 and lens[-1] == 0
+    buf = torch.from_numpy(np.concatenate(parts)).to(CUDA)
+    tptr = [torch.from_numpy(flat[n]) for n in ext.ROUND_TPTR_NAMES]
+    name, args, _ = b.backend._family_call(b.spec, CUDA)
+    assert name == "logreg"
+
+    def call(buf, lens, tptr):
+        ext.run_round_logreg(
+            b.state.params, b.state.ages, b.pool.slots, b.pool.slot_ages,
+            buf, lens, *tptr, b.data.x, b.data.y, b.data.counts, *args)
+
+    def state():
+        torch.cuda.synchronize()
+        return [t.clone() for t in (b.state.params, b.state.ages,
+                                    b.pool.slots, b.pool.slot_ages)]
+
+    # every bad call changes the last array only (rep_reply_slots, which a
+    # round without replies never reads) or a tick pointer's tail
+    before = state()
+    bad = {
+        "lens one short": (buf, lens[:-1], tptr),
+        "negative length": (buf, lens[:-1] + [-1], tptr),
+        "lens past the buffer": (buf, lens[:-1] + [1], tptr),
+        "lens far past the buffer": (buf, lens[:-1] + [2 ** 62], tptr),
+        "host buffer": (buf.cpu(), lens, tptr),
+        "unequal tick pointers": (
+            buf, lens, tptr[:-1] + [torch.zeros(3, dtype=torch.int32)]),
+        "empty tick pointers": (
+            buf, lens, [torch.zeros(0, dtype=torch.int32)] * 4),
+    }
+    for what, (bb, ll, tt) in bad.items():
+        with pytest.raises(RuntimeError):
+            call(bb, ll, tt)
+        for x, y in zip(before, state()):
+            assert torch.equal(x, y), what
+
+    call(buf, lens, tptr)
+    torch.cuda.synchronize()
+    assert not torch.equal(b.state.params, start)  # node 5 merged and trained
+    assert torch.equal(b.state.params[:5], start[:5])
+    assert torch.equal(a.state.params, b.state.params)
+    assert torch.equal(a.state.ages, b.state.ages)
+    assert torch.equal(a.pool.slots, b.pool.slots)
+    assert torch.equal(a.pool.slot_ages, b.pool.slot_ages)
+
+
 def test_construct_destroy_twenty(monkeypatch):
     spec = _spec()
     cfg, data = _cfg(spec, sampling_eval=0.5), _data()

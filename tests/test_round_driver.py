@@ -25,13 +25,32 @@ pytestmark = pytest.mark.skipif(
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N_ROUNDS = 30
 
-# the upload order (BatchedGossipSimulator._run_round_fast's dev_names)
+# the upload order, pinned here: the table of csrc/round_source.h has to
+# say the same (test_array_table_is_the_one_definition)
 DEV_NAMES = (
     "snap_nodes", "snap_slots", "recv_nodes", "recv_nptr", "del_slots",
     "reply_slots", "pull_nodes", "pull_slots", "rep_nodes", "rep_nptr",
     "rep_slots", "del_pids", "rep_pids", "rep_reply_slots",
 )
 TPTRS = ("snap_tptr", "recv_tptr", "pull_tptr", "rep_tptr")
+
+
+def test_array_table_is_the_one_definition():
+    import inspect
+
+    from gossipy_amd.engine.runner import BatchedGossipSimulator
+
+    # both extensions export the table they were compiled with
+    for mod in (ops.load_sched(), ops.load_extension()):
+        assert mod.ROUND_ARRAY_NAMES == DEV_NAMES
+        assert mod.ROUND_TPTR_NAMES == TPTRS
+    # and the Python path's upload reads it from the extension it calls,
+    # with no list of its own
+    src = inspect.getsource(BatchedGossipSimulator._run_round_fast)
+    assert "for n in ext.ROUND_ARRAY_NAMES" in src
+    assert "for n in ext.ROUND_TPTR_NAMES" in src
+    for name in DEV_NAMES + TPTRS:
+        assert name not in src, name
 
 
 def _cfgs():
