@@ -30,6 +30,10 @@
 //                           (LimitedMergeMixin._merge,
 //                           gossipy/model/handler.py:690-715) in place of
 //                           the mean; see lim_rule.
+//   tick_logreg_big_kernel, tick_logreg_lim_big_kernel, <BIG = true>
+//                         — the logreg kernels for batches of more rows
+//                           than their 128 threads (full-shard batches of
+//                           large shards); picked host-side, see big_batch.
 //
 // Models are tiny (57x2 logreg ... few-hundred-wide MLPs); per-launch work
 // is launch-latency bound, so kernels are built to let ONE launch cover all
@@ -301,6 +305,11 @@ DEV_INLINE float col_chain(const float* p, int ps, const float* q, int qs,
 // Minibatch SGD epochs over the node's shard, on the LDS-resident model W.
 // xb/dz are LDS scratch; age is a wave-uniform register; c = counts[node],
 // read once by the caller.
+// BIG = a batch may have more rows than the block has threads: the
+// per-sample stage strides over the batch. The host picks the instantiation
+// from the largest batch (big_batch), so the default one, which every shard
+// of at most blockDim rows runs, keeps its one-pass stage.
+template <bool BIG = false>
 DEV_INLINE void logreg_update(const LogregArgs& a, int node, int c, float* W,
                               float* xb, float* dz, int& age,
                               int prestaged = 0)
@@ -333,11 +342,11 @@ DEV_INLINE void logreg_update(const LogregArgs& a, int node, int c, float* W,
                                    W + kk * a.d, xb + s * a.d, a.d);
             }
             __syncthreads();
-            // dLoss/dz (thread = sample), in place over the sample's own k
-            // scores: a = sigmoid(z); p = softmax(a);
+            // dLoss/dz of sample s with label y, in place over the sample's
+            // own k scores: a = sigmoid(z); p = softmax(a);
             // dz = (p - 1_y)/m * a*(1-a)
-            if (tid < m) {
-                float* zs = dz + tid * a.k;
+            auto dz_row = [&](int s, float y) __attribute__((always_inline)) {
+                float* zs = dz + s * a.k;
                 float amax = -1e30f;
                 for (int kk = 0; kk < a.k; ++kk) {
                     float sg = 1.0f / (1.0f + __expf(-zs[kk]));
@@ -346,7 +355,7 @@ DEV_INLINE void logreg_update(const LogregArgs& a, int node, int c, float* W,
                 }
                 float sum = 0.f;
                 for (int kk = 0; kk < a.k; ++kk) sum += __expf(zs[kk] - amax);
-                int yi = (int)yv;
+                int yi = (int)y;
                 float inv = 1.0f / sum;
                 for (int kk = 0; kk < a.k; ++kk) {
                     float sg = zs[kk];
@@ -354,6 +363,12 @@ DEV_INLINE void logreg_update(const LogregArgs& a, int node, int c, float* W,
                     float g = pk * inv - (kk == yi ? 1.0f : 0.0f);
                     zs[kk] = (g / m) * sg * (1.0f - sg);
                 }
+            };
+            // thread = sample; the first pass uses the prefetched label
+            if (tid < m) dz_row(tid, yv);
+            if constexpr (BIG) {
+                for (int s = tid + blockDim.x; s < m; s += blockDim.x)
+                    dz_row(s, Yn[s0 + s]);
             }
             __syncthreads();
             // SGD step (thread = parameter)
@@ -376,7 +391,7 @@ DEV_INLINE void logreg_update(const LogregArgs& a, int node, int c, float* W,
 // LIM = limited merge: every mean merge below becomes lim_rule on the two
 // ages at that point. The plain instantiation compiles to the mean-merge
 // code unchanged.
-template <bool LIM>
+template <bool LIM, bool BIG = false>
 DEV_INLINE void logreg_process_node(const LogregArgs& a, int i)
 {
     int node = a.nodes[i];
@@ -444,7 +459,7 @@ DEV_INLINE void logreg_process_node(const LogregArgs& a, int i)
             }
         };
         issue_pre(j0 + 1);
-        logreg_update(a, node, c, W, xb, dz, age, /*prestaged=*/1);
+        logreg_update<BIG>(a, node, c, W, xb, dz, age, /*prestaged=*/1);
         int rs0 = a.rslots ? a.rslots[j0] : -1;
         if (rs0 >= 0) {  // first delivery's PUSH_PULL reply snapshot
             copy_row(a.slots + (long)rs0 * a.D, W, a.D);
@@ -487,7 +502,7 @@ DEV_INLINE void logreg_process_node(const LogregArgs& a, int i)
                 age = max(age, pre_age);
                 __syncthreads();
                 issue_pre(j + 1);
-                logreg_update(a, node, c, W, xb, dz, age, /*prestaged=*/xb_keep);
+                logreg_update<BIG>(a, node, c, W, xb, dz, age, /*prestaged=*/xb_keep);
             } else {  // PASS (pass-through coin resolved to adopt)
                 copy_row(W, srow2, a.D);
                 age = a.slot_ages[slot2];
@@ -512,7 +527,7 @@ DEV_INLINE void logreg_process_node(const LogregArgs& a, int i)
     int age = a.ages[node];
 
     if (a.update_only) {
-        logreg_update(a, node, c, W, xb, dz, age);
+        logreg_update<BIG>(a, node, c, W, xb, dz, age);
     } else {
         for (int j = a.ptr[i]; j < a.ptr[i + 1]; ++j) {
             int slot = a.dslots[j];
@@ -531,19 +546,19 @@ DEV_INLINE void logreg_process_node(const LogregArgs& a, int i)
                 }
                 age = max(age, sage);
                 __syncthreads();
-                logreg_update(a, node, c, W, xb, dz, age);
+                logreg_update<BIG>(a, node, c, W, xb, dz, age);
             } else if (md == MODE_UPDATE) {
                 // adopt the received model, then train it
                 copy_row(W, srow, a.D);
                 age = sage;
                 __syncthreads();
-                logreg_update(a, node, c, W, xb, dz, age);
+                logreg_update<BIG>(a, node, c, W, xb, dz, age);
             } else if (md == MODE_UPDATE_MERGE) {
-                logreg_update(a, node, c, W, xb, dz, age);
+                logreg_update<BIG>(a, node, c, W, xb, dz, age);
                 copy_row(W2, srow, a.D);
                 __syncthreads();
                 int age2 = sage;
-                logreg_update(a, node, c, W2, xb, dz, age2);
+                logreg_update<BIG>(a, node, c, W2, xb, dz, age2);
                 if constexpr (LIM) {
                     // the rule sees the two post-training ages
                     lim_merge_row(lim_rule(age, age2, a.lim), W, W2, a.D);
@@ -583,6 +598,19 @@ __global__ void __launch_bounds__(128)
 tick_logreg_lim_kernel(LogregArgs a)
 {
     logreg_process_node<true>(a, blockIdx.x);
+}
+
+// the same two for batches of more rows than the block has threads
+__global__ void __launch_bounds__(128)
+tick_logreg_big_kernel(LogregArgs a)
+{
+    logreg_process_node<false, true>(a, blockIdx.x);
+}
+
+__global__ void __launch_bounds__(128)
+tick_logreg_lim_big_kernel(LogregArgs a)
+{
+    logreg_process_node<true, true>(a, blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------
@@ -675,12 +703,14 @@ DEV_INLINE void logreg_part_update(const LogregPartArgs& a, int node, float* W,
             // self.n_updates += 1 happens before the step (handler.py:506)
             for (int p = tid; p < a.P; p += blockDim.x) agev[p] += 1;
             __syncthreads();
-            if (tid < m) {
+            // thread = sample, block-strided: a batch may have more rows
+            // than the block has threads
+            for (int s = tid; s < m; s += blockDim.x) {
                 float z[KMAX];
                 for (int kk = 0; kk < a.k; ++kk) {
                     float acc = W[a.k * a.d + kk];
                     const float* wrow = W + kk * a.d;
-                    const float* xrow = xs + tid * a.d;
+                    const float* xrow = xs + s * a.d;
                     for (int dd = 0; dd < a.d; ++dd) acc += wrow[dd] * xrow[dd];
                     z[kk] = acc;
                 }
@@ -695,11 +725,11 @@ DEV_INLINE void logreg_part_update(const LogregPartArgs& a, int node, float* W,
                     p[kk] = __expf(z[kk] - amax);
                     sum += p[kk];
                 }
-                int yi = (int)Yn[s0 + tid];
+                int yi = (int)Yn[s0 + s];
                 float inv = 1.0f / sum;
                 for (int kk = 0; kk < a.k; ++kk) {
                     float g = p[kk] * inv - (kk == yi ? 1.0f : 0.0f);
-                    dz[tid * a.k + kk] = (g / m) * z[kk] * (1.0f - z[kk]);
+                    dz[s * a.k + kk] = (g / m) * z[kk] * (1.0f - z[kk]);
                 }
             }
             __syncthreads();
@@ -868,6 +898,7 @@ DEV_INLINE void logreg_samp_merge(const LogregSampArgs& a, float* W, float* W3,
     __syncthreads();
 }
 
+template <bool BIG>  // as logreg_update's
 __global__ void __launch_bounds__(128)
 tick_logreg_samp_kernel(LogregSampArgs a)
 {
@@ -895,7 +926,7 @@ tick_logreg_samp_kernel(LogregSampArgs a)
     int cn = a.counts[node];
 
     if (a.update_only) {
-        logreg_update(u, node, cn, W, xb, dz, age);
+        logreg_update<BIG>(u, node, cn, W, xb, dz, age);
     } else {
         for (int j = a.ptr[i]; j < a.ptr[i + 1]; ++j) {
             int slot = a.dslots[j];
@@ -904,17 +935,17 @@ tick_logreg_samp_kernel(LogregSampArgs a)
             int sage = a.slot_ages[slot];
             if (a.mode == MODE_MERGE_UPDATE) {
                 logreg_samp_merge(a, W, W3, srow, seed);
-                logreg_update(u, node, cn, W, xb, dz, age);
+                logreg_update<BIG>(u, node, cn, W, xb, dz, age);
             } else {
                 // UPDATE: train received, merge its sample into self
                 // (handler.py:440-442); UPDATE_MERGE: self-update first
                 // (handler.py:445-448)
                 if (a.mode == MODE_UPDATE_MERGE)
-                    logreg_update(u, node, cn, W, xb, dz, age);
+                    logreg_update<BIG>(u, node, cn, W, xb, dz, age);
                 for (int e = tid; e < a.D; e += blockDim.x) W2[e] = srow[e];
                 __syncthreads();
                 int age2 = sage;
-                logreg_update(u, node, cn, W2, xb, dz, age2);
+                logreg_update<BIG>(u, node, cn, W2, xb, dz, age2);
                 logreg_samp_merge(a, W, W3, W2, seed);
             }
             int rs = a.rslots ? a.rslots[j] : -1;
@@ -1478,17 +1509,19 @@ DEV_INLINE void mlp_update(const MlpArgs& a, int node, float* W,
             // ---- output grad: softmax-CE on the raw head
             int k = a.layout[4 * (a.n_layers - 1) + 3];
             float* gcur = grad;  // [m, k] for the head, reused per layer
-            if (tid < m) {
-                const float* z = cur + tid * k;
+            // (thread = sample, block-strided: a batch may have more rows
+            // than the block has threads)
+            for (int s = tid; s < m; s += blockDim.x) {
+                const float* z = cur + s * k;
                 float zmax = -1e30f;
                 for (int kk = 0; kk < k; ++kk) zmax = fmaxf(zmax, z[kk]);
                 float sum = 0.f;
                 for (int kk = 0; kk < k; ++kk) sum += __expf(z[kk] - zmax);
-                int yi = (int)Yn[s0 + tid];
+                int yi = (int)Yn[s0 + s];
                 float inv = 1.0f / sum;
                 for (int kk = 0; kk < k; ++kk) {
                     float p = __expf(z[kk] - zmax) * inv;
-                    gcur[tid * k + kk] = (p - (kk == yi ? 1.0f : 0.0f)) / m;
+                    gcur[s * k + kk] = (p - (kk == yi ? 1.0f : 0.0f)) / m;
                 }
             }
             __syncthreads();
@@ -2100,6 +2133,7 @@ struct PensArgs {
     int epochs, bs;
 };
 
+template <bool BIG>  // as logreg_update's
 __global__ void __launch_bounds__(128)
 tick_pens_kernel(PensArgs a)
 {
@@ -2182,7 +2216,7 @@ tick_pens_kernel(PensArgs a)
     u.X = a.X; u.Y = a.Y; u.counts = a.dcounts;
     u.d = a.d; u.k = a.k; u.Smax = a.Smax; u.D = a.D;
     u.lr = a.lr; u.wd = a.wd; u.epochs = a.epochs; u.bs = a.bs;
-    logreg_update(u, node, c_n, W, xb, dz, age);
+    logreg_update<BIG>(u, node, c_n, W, xb, dz, age);
     __syncthreads();
     for (int e = tid; e < a.D; e += blockDim.x)
         a.params[(long)node * a.D + e] = W[e];
@@ -2221,6 +2255,7 @@ DEV_INLINE void round_sync()
     }
 }
 
+template <bool BIG>  // as logreg_update's
 __global__ void __launch_bounds__(128)
 coop_round_logreg_kernel(CoopRoundArgs c)
 {
@@ -2256,7 +2291,7 @@ coop_round_logreg_kernel(CoopRoundArgs c)
             a.dslots = c.del_slots;
             a.rslots = c.reply_slots;
             for (int i = r0 + bid; i < r1; i += nb) {
-                logreg_process_node<false>(a, i);
+                logreg_process_node<false, BIG>(a, i);
                 __syncthreads();
             }
             dirty = true;
@@ -2280,7 +2315,7 @@ coop_round_logreg_kernel(CoopRoundArgs c)
             a.dslots = c.rep_slots;
             a.rslots = nullptr;
             for (int i = q0 + bid; i < q1; i += nb) {
-                logreg_process_node<false>(a, i);
+                logreg_process_node<false, BIG>(a, i);
                 __syncthreads();
             }
             dirty = true;
@@ -2555,6 +2590,14 @@ static int batch_rows(int64_t bs, int Smax)
     return (bs == 0) ? Smax : std::min<int>(bs, Smax);
 }
 
+// the logreg kernels run LOGREG_THREADS threads, one per sample in the
+// dLoss/dz stage; a larger batch needs the BIG instantiation, which strides
+constexpr int LOGREG_THREADS = 128;
+static bool big_batch(int64_t bs, int Smax)
+{
+    return batch_rows(bs, Smax) > LOGREG_THREADS;
+}
+
 // merge_limit of a plan: -1 = plain mean merge, L >= 0 = limited merge.
 // Ages are int32 and the rule adds L to one, so L is kept far below 2^31.
 static int check_merge_limit(int64_t merge_limit)
@@ -2584,8 +2627,13 @@ static Plan<LogregArgs> logreg_plan(
     int bsmax = batch_rows(bs, a.Smax);
     L.smem = sizeof(float) * (2 * a.D + (size_t)bsmax * a.d + (size_t)bsmax * a.k);
     TORCH_CHECK(L.smem <= 160 * 1024, "logreg LDS budget exceeded: ", L.smem);
-    L.kernel = (merge_limit >= 0) ? tick_logreg_lim_kernel : tick_logreg_kernel;
-    L.threads = 128;
+    if (big_batch(bs, a.Smax))
+        L.kernel = (merge_limit >= 0) ? tick_logreg_lim_big_kernel
+                                      : tick_logreg_big_kernel;
+    else
+        L.kernel = (merge_limit >= 0) ? tick_logreg_lim_kernel
+                                      : tick_logreg_kernel;
+    L.threads = LOGREG_THREADS;
     L.snap = {a.D, a.D, 0, 1};
     return L;
 }
@@ -2655,8 +2703,9 @@ static Plan<LogregSampArgs> logreg_samp_plan(
     L.smem = sizeof(float) * (3 * a.D + (size_t)bsmax * a.d +
                               (size_t)bsmax * a.k);
     TORCH_CHECK(L.smem <= 160 * 1024, "sampled logreg LDS budget exceeded: ", L.smem);
-    L.kernel = tick_logreg_samp_kernel;
-    L.threads = 128;
+    L.kernel = big_batch(bs, a.Smax) ? tick_logreg_samp_kernel<true>
+                                     : tick_logreg_samp_kernel<false>;
+    L.threads = LOGREG_THREADS;
     L.snap = {a.D, a.D, 0, 1};
     return L;
 }
@@ -3195,8 +3244,10 @@ static void run_round_logreg(
     auto L = logreg_plan(c.st, d, k, lr, wd, epochs, bs, mode, merge_limit);
     // the single-workgroup round kernel has no limited-merge instantiation
     if (merge_limit < 0 &&
-        single_block_round(coop_round_logreg_kernel, L, c.r, c.tptr,
-                           c.st.params.device()))
+        single_block_round(big_batch(bs, L.a.Smax)
+                               ? coop_round_logreg_kernel<true>
+                               : coop_round_logreg_kernel<false>,
+                           L, c.r, c.tptr, c.st.params.device()))
         return;
     stream_round(L, c.r);
 }
@@ -3277,11 +3328,14 @@ static void run_round_coop_logreg(
 {
     auto L = logreg_plan(rc.st, d, k, lr, wd, epochs, bs, mode);
     CoopRoundArgs c = round_args<CoopRoundArgs>(L.a, rc.r);
+    const void* kernel = big_batch(bs, L.a.Smax)
+        ? (const void*)coop_round_logreg_kernel<true>
+        : (const void*)coop_round_logreg_kernel<false>;
     int grid = std::max<int>(1, (int)max_batch);
     // stay within guaranteed cooperative residency
     int max_blocks = 0;
     hipError_t oerr = hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &max_blocks, (const void*)coop_round_logreg_kernel, L.threads, L.smem);
+        &max_blocks, kernel, L.threads, L.smem);
     TORCH_CHECK(oerr == hipSuccess, "occupancy query failed");
     hipDeviceProp_t prop;
     (void)hipGetDeviceProperties(&prop, 0);
@@ -3290,7 +3344,7 @@ static void run_round_coop_logreg(
     if (grid > limit) grid = limit;
     void* kargs[] = {&c};
     hipError_t err = hipLaunchCooperativeKernel(
-        (const void*)coop_round_logreg_kernel, dim3(grid), dim3(L.threads),
+        kernel, dim3(grid), dim3(L.threads),
         kargs, L.smem, current_stream());
     TORCH_CHECK(err == hipSuccess, "cooperative launch failed: ",
                 hipGetErrorString(err));
@@ -3326,8 +3380,10 @@ void tick_pens(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
     size_t smem = sizeof(float) * (a.D + (size_t)bsmax * a.d +
                                    (size_t)bsmax * a.k);
     TORCH_CHECK(smem <= 160 * 1024, "pens LDS budget exceeded: ", smem);
-    hipLaunchKernelGGL(tick_pens_kernel, dim3(n), dim3(128), smem,
-                       current_stream(), a);
+    hipLaunchKernelGGL(big_batch(bs, a.Smax) ? tick_pens_kernel<true>
+                                             : tick_pens_kernel<false>,
+                       dim3(n), dim3(LOGREG_THREADS), smem, current_stream(),
+                       a);
 }
 
 // Scoring-mode launch geometry from a.D, a.d and a.n_eval: sets a.tile and
