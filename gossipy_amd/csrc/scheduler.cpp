@@ -799,6 +799,35 @@ protected:
         }
         return out;
     }
+    // pend_take into storage the caller keeps: with the ring, the slot and
+    // `out` trade buffers, so neither regrows from nothing on the next tick
+    void pend_take_into(int64_t t, std::vector<Msg>& out)
+    {
+        out.clear();
+        if (ring_mask_) {
+            size_t sl = (size_t)t & ring_mask_;
+            if (ring_tick_[sl] == t) {
+                out.swap(ring_[sl]);
+                ring_tick_[sl] = INT64_MIN;
+            }
+        } else {
+            auto it = pending_.find(t);
+            if (it != pending_.end()) {
+                out = std::move(it->second);
+                pending_.erase(it);
+            }
+        }
+    }
+    // generate_round's per-tick scratch, cleared and never freed, and the
+    // sizes of the last round's output arrays, which the next round
+    // reserves
+    struct TickScratch {
+        std::vector<int32_t> firing, freed, peers, pids, order, rorder;
+        std::vector<double> online, u, drop_u;
+        std::vector<int64_t> delays;
+        std::vector<Msg> due, rep_due;
+        size_t snap = 0, recv = 0, del = 0, pull = 0, rep = 0, rep_del = 0;
+    } sc_;
     // consumed slots re-enter circulation only slot_reuse_lag_ ticks after
     // the tick that freed them (FIFO), mirroring Scheduler.SLOT_REUSE_LAG.
     // The effective lag is max(32, delta): launch groups never span a
@@ -1034,27 +1063,44 @@ RoundData NativeScheduler::generate_round(int64_t r)
     auto &rep_slots = rd.rep_slots, &rep_owners = rd.rep_owners,
          &rep_pids = rd.rep_pids;
 
-    std::vector<double> online(n_);
-    std::vector<int32_t> firing;
-    firing.reserve(64);
+    const size_t n_ticks = (size_t)delta_ + 1;
+    snap_nodes.reserve(sc_.snap); snap_slots.reserve(sc_.snap);
+    snap_tptr.reserve(n_ticks);
+    recv_nodes.reserve(sc_.recv); recv_nptr.reserve(sc_.recv + 1);
+    recv_tptr.reserve(n_ticks);
+    del_slots.reserve(sc_.del); del_owners.reserve(sc_.del);
+    reply_slots.reserve(sc_.del); del_pids.reserve(sc_.del);
+    pull_nodes.reserve(sc_.pull); pull_slots.reserve(sc_.pull);
+    pull_tptr.reserve(n_ticks);
+    rep_nodes.reserve(sc_.rep); rep_nptr.reserve(sc_.rep + 1);
+    rep_tptr.reserve(n_ticks);
+    rep_slots.reserve(sc_.rep_del); rep_owners.reserve(sc_.rep_del);
+    rep_pids.reserve(sc_.rep_del);
+
+    auto &online = sc_.online, &u = sc_.u, &drop_u = sc_.drop_u;
+    auto &freed = sc_.freed, &peers = sc_.peers, &pids = sc_.pids,
+         &order = sc_.order, &rorder = sc_.rorder;
+    auto& delays = sc_.delays;
+    auto &due = sc_.due, &rep_due = sc_.rep_due;
+    if (online_ < 1.0) online.resize((size_t)n_);
 
     for (int64_t t = t0; t < t1; ++t) {
-        std::vector<int32_t> freed;
+        freed.clear();
 
         // --- firing set (ascending node id, like np.where)
-        firing.clear();
-        if (sync_) {
-            firing = fire_buckets_[t % delta_];
-        } else {
+        if (!sync_) {
+            sc_.firing.clear();
             for (int64_t i = 0; i < n_; ++i)
-                if (t % deltas_[i] == 0) firing.push_back((int32_t)i);
+                if (t % deltas_[i] == 0) sc_.firing.push_back((int32_t)i);
         }
+        const std::vector<int32_t>& firing =
+            sync_ ? fire_buckets_[t % delta_] : sc_.firing;
 
         // --- sends (gossipy/simul.py:393-407 equivalent)
         size_t n_f = firing.size();
         if (n_f) {
             Stream gp(stream_key(seed_, PEER, (uint64_t)t, 0));
-            std::vector<int32_t> peers(n_f);
+            peers.resize(n_f);
             if (indptr_.empty()) {
                 for (size_t j = 0; j < n_f; ++j) {
                     int64_t draw = gp.integers(0, n_ - 1);
@@ -1062,7 +1108,7 @@ RoundData NativeScheduler::generate_round(int64_t r)
                 }
             } else {
                 // python draws ALL uniforms in one batch before indexing
-                std::vector<double> u(n_f);
+                u.resize(n_f);
                 for (size_t j = 0; j < n_f; ++j) u[j] = gp.rnd();
                 for (size_t j = 0; j < n_f; ++j) {
                     int64_t s = indptr_[firing[j]];
@@ -1071,18 +1117,18 @@ RoundData NativeScheduler::generate_round(int64_t r)
                                                           u[j] * (double)deg)];
                 }
             }
-            std::vector<double> drop_u(n_f, 1.0);
+            drop_u.assign(n_f, 1.0);
             if (drop_ > 0.0) {
                 Stream gdrop(stream_key(seed_, DROP, (uint64_t)t, 0));
                 for (size_t j = 0; j < n_f; ++j) drop_u[j] = gdrop.rnd();
             }
             int64_t msize = (proto_ == PULL) ? 1 : model_size_;
-            std::vector<int64_t> delays(n_f);
+            delays.resize(n_f);
             {
                 Stream gdl(stream_key(seed_, DELAY, (uint64_t)t, 0));
                 for (size_t j = 0; j < n_f; ++j) delays[j] = delay_for(gdl, msize);
             }
-            std::vector<int32_t> pids(n_f, -1);
+            pids.assign(n_f, -1);
             if (n_parts_ > 0) {
                 Stream gpt(stream_key(seed_, PART, (uint64_t)t, 0));
                 for (size_t j = 0; j < n_f; ++j)
@@ -1104,9 +1150,9 @@ RoundData NativeScheduler::generate_round(int64_t r)
                 sent += 1;
                 total_size += msize;
                 if (drop_u[j] >= drop_) {
-                    int64_t due = t + delays[j];
+                    int64_t due_t = t + delays[j];
                     int32_t rf = (proto_ == PUSH_PULL) ? -2 : -1;
-                    pend_push(due, {receiver, slot, rf, is_pull, sender, pids[j]});
+                    pend_push(due_t, {receiver, slot, rf, is_pull, sender, pids[j]});
                 } else {
                     failed += 1;
                     if (slot >= 0) freed.push_back(slot);
@@ -1122,9 +1168,9 @@ RoundData NativeScheduler::generate_round(int64_t r)
         }
         // online_ >= 1.0: nobody is ever offline — the comparison below is
         // guarded, so the n-wide per-tick fill is skipped entirely
-        std::vector<Msg> due = pend_take(t);
+        pend_take_into(t, due);
         // receiver -> (slot, rslot, sender) in first-appearance order
-        std::vector<int32_t> order;
+        order.clear();
         ev_pool_.clear(); row_head_.clear(); row_tail_.clear();
         const int64_t st_main = 2 * t;
         auto row_append = [&](int64_t stamp, int32_t node, int32_t a,
@@ -1183,8 +1229,8 @@ RoundData NativeScheduler::generate_round(int64_t r)
         pull_tptr.push_back((int32_t)pull_nodes.size());
 
         // --- sub-phase C: same-tick replies
-        std::vector<Msg> rep_due = pend_take(t);
-        std::vector<int32_t> rorder;
+        pend_take_into(t, rep_due);
+        rorder.clear();
         ev_pool_.clear(); row_head_.clear(); row_tail_.clear();
         const int64_t st_rep = 2 * t + 1;
         auto rep_append = [&](int32_t node, int32_t a, int32_t b, int32_t c) {
@@ -1224,6 +1270,9 @@ RoundData NativeScheduler::generate_round(int64_t r)
         for (int32_t s : freed) reuse_q_.emplace_back(t, s);
     }
 
+    sc_.snap = snap_nodes.size(); sc_.recv = recv_nodes.size();
+    sc_.del = del_slots.size(); sc_.pull = pull_nodes.size();
+    sc_.rep = rep_nodes.size(); sc_.rep_del = rep_slots.size();
     rd.n_slots = next_slot_;
     if (sampling_eval_ > 0) {
         Stream g(stream_key(seed_, EVAL, (uint64_t)(t1 - 1), 0));

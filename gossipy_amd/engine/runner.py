@@ -1415,7 +1415,8 @@ class BatchedGossipSimulator(SimulationEventSender):
         global-set evaluation; ``GOSSIPY_NO_ROUND_DRIVER=1`` turns it off
         (A/B; ``GOSSIPY_RD_NO_MAPPED_EVAL=1`` and
         ``GOSSIPY_RD_NO_SIDE_UPLOAD=1`` turn off its two measured options
-        one by one).
+        one by one, ``GOSSIPY_RD_EVAL_OVERLAP=1`` turns on the third, which
+        is off by default).
 
         The driver does the work of ``_run_round_fast`` and ``_evaluate``
         without calling them. So a subclass that overrides either, or a
@@ -1467,6 +1468,7 @@ class BatchedGossipSimulator(SimulationEventSender):
                 eval_all=not self.cfg.sampling_eval > 0,
                 mapped_metrics=env.get("GOSSIPY_RD_NO_MAPPED_EVAL") != "1",
                 side_upload=env.get("GOSSIPY_RD_NO_SIDE_UPLOAD") != "1",
+                eval_overlap=env.get("GOSSIPY_RD_EVAL_OVERLAP") == "1",
             )
             self._rd_key = key
             self._rd_pool = self.pool.slots

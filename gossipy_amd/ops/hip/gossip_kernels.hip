@@ -34,6 +34,13 @@
 //                         — the logreg kernels for batches of more rows
 //                           than their 128 threads (full-shard batches of
 //                           large shards); picked host-side, see big_batch.
+//   tick_logreg_*thin_kernel
+//                         — the four logreg kernels with the pipelined
+//                           update (dot_chain_pipe, col_chain_exact,
+//                           dz_row_regs): a shorter dependent chain for
+//                           more registers; picked host-side for launches
+//                           of at most one wave per SIMD, see
+//                           thin_launch_rows.
 //
 // Models are tiny (57x2 logreg ... few-hundred-wide MLPs); per-launch work
 // is launch-latency bound, so kernels are built to let ONE launch cover all
@@ -302,6 +309,125 @@ DEV_INLINE float col_chain(const float* p, int ps, const float* q, int qs,
     return g;
 }
 
+// dot_chain with two register sets: the
+// reads of chunk n+1 are in flight under the FMAs of chunk n. d must be
+// wave-uniform: the tail reads and adds exactly d % CH elements behind
+// scalar branches.
+DEV_INLINE float dot_chain_pipe(float acc, const float* w, const float* x, int d)
+{
+    float wa[CH], xa[CH], wb[CH], xb[CH];
+    auto load = [&](float* wv, float* xv, int e) __attribute__((always_inline)) {
+#pragma unroll
+        for (int u = 0; u < CH; ++u) { wv[u] = w[e + u]; xv[u] = x[e + u]; }
+    };
+    auto fma = [&](const float* wv, const float* xv) __attribute__((always_inline)) {
+#pragma unroll
+        for (int u = 0; u < CH; ++u) acc = fmaf(wv[u], xv[u], acc);
+    };
+    int e0 = 0;
+    if (CH <= d) load(wa, xa, 0);
+    // set a holds chunk e0; the body has no branch, so each FMA block waits
+    // only for its own set's reads. The fences pin that order: the
+    // scheduler otherwise sinks each set's reads into the FMAs before it.
+    for (; e0 + 3 * CH <= d; e0 += 2 * CH) {
+        load(wb, xb, e0 + CH);
+        __builtin_amdgcn_sched_barrier(0);
+        fma(wa, xa);
+        __builtin_amdgcn_sched_barrier(0);
+        load(wa, xa, e0 + 2 * CH);
+        __builtin_amdgcn_sched_barrier(0);
+        fma(wb, xb);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    // one or two whole chunks are left when d >= CH, the first of them in a
+    if (e0 + 2 * CH <= d) {
+        load(wb, xb, e0 + CH);
+        fma(wa, xa);
+        fma(wb, xb);
+        e0 += 2 * CH;
+    } else if (e0 + CH <= d) {
+        fma(wa, xa);
+        e0 += CH;
+    }
+    // one tail for every path: the d - e0 < CH elements, into set b
+    int r = d - e0;
+#pragma unroll
+    for (int u = 0; u < CH - 1; ++u) {
+        if (u >= r) break;
+        wb[u] = w[e0 + u]; xb[u] = x[e0 + u];
+    }
+#pragma unroll
+    for (int u = 0; u < CH - 1; ++u) {
+        if (u >= r) break;
+        acc = fmaf(wb[u], xb[u], acc);
+        // a real scalar branch, not an FMA masked by a select
+        asm volatile("" : "+v"(acc));
+    }
+    return acc;
+}
+
+// col_chain (Q false: its q == nullptr form) whose short last chunk reads
+// no clamped element and adds behind no select. m >= 1 is
+// the same in every thread of the block: a short last chunk reads and adds
+// exactly its own elements behind scalar branches.
+template <bool Q = true>  // false: no q, the sum of p alone
+DEV_INLINE float col_chain_exact(const float* p, int ps, const float* q, int qs,
+                           int m)
+{
+    m = __builtin_amdgcn_readfirstlane(m);
+    float g = 0.f;
+    for (int s0 = 0; s0 < m; s0 += CH) {
+        float pv[CH], qv[CH];
+        int r = min(CH, m - s0);
+#pragma unroll
+        for (int u = 0; u < CH; ++u) {
+            if (u >= r) break;
+            pv[u] = p[(s0 + u) * ps];
+            if constexpr (Q) qv[u] = q[(s0 + u) * qs];
+        }
+#pragma unroll
+        for (int u = 0; u < CH; ++u) {
+            if (u >= r) break;
+            if constexpr (Q) g = fmaf(pv[u], qv[u], g); else g += pv[u];
+            // a real scalar branch, not an add masked by a select
+            asm volatile("" : "+v"(g));
+        }
+    }
+    return g;
+}
+
+// dLoss/dz of one sample for a compile-time class count: the K scores are
+// read once, every pass runs on registers with static indices, the K
+// results are written once. The operations and their order are those of the
+// generic loop in logreg_update, which recomputes exp(sg - amax) where this
+// keeps it.
+template <int K>
+DEV_INLINE void dz_row_regs(float* zs, float y, int m)
+{
+    float sg[K], pk[K];
+#pragma unroll
+    for (int kk = 0; kk < K; ++kk) sg[kk] = zs[kk];
+    float amax = -1e30f;
+#pragma unroll
+    for (int kk = 0; kk < K; ++kk) {
+        sg[kk] = 1.0f / (1.0f + __expf(-sg[kk]));
+        amax = fmaxf(amax, sg[kk]);
+    }
+    float sum = 0.f;
+#pragma unroll
+    for (int kk = 0; kk < K; ++kk) {
+        pk[kk] = __expf(sg[kk] - amax);
+        sum += pk[kk];
+    }
+    int yi = (int)y;
+    float inv = 1.0f / sum;
+#pragma unroll
+    for (int kk = 0; kk < K; ++kk) {
+        float g = pk[kk] * inv - (kk == yi ? 1.0f : 0.0f);
+        zs[kk] = (g / m) * sg[kk] * (1.0f - sg[kk]);
+    }
+}
+
 // Minibatch SGD epochs over the node's shard, on the LDS-resident model W.
 // xb/dz are LDS scratch; age is a wave-uniform register; c = counts[node],
 // read once by the caller.
@@ -309,7 +435,11 @@ DEV_INLINE float col_chain(const float* p, int ps, const float* q, int qs,
 // per-sample stage strides over the batch. The host picks the instantiation
 // from the largest batch (big_batch), so the default one, which every shard
 // of at most blockDim rows runs, keeps its one-pass stage.
-template <bool BIG = false>
+// PIPE = the forward and the reductions run through dot_chain_pipe and
+// col_chain_exact and a two-class dLoss/dz row through dz_row_regs: the same
+// arithmetic in the same order, a shorter chain per delivery, about 40 more
+// VGPRs. Only the thin instantiations of the tick kernels use it.
+template <bool BIG = false, bool PIPE = false>
 DEV_INLINE void logreg_update(const LogregArgs& a, int node, int c, float* W,
                               float* xb, float* dz, int& age,
                               int prestaged = 0)
@@ -338,8 +468,11 @@ DEV_INLINE void logreg_update(const LogregArgs& a, int node, int c, float* W,
             // block, parked in the dz area
             for (int pr = tid; pr < m * a.k; pr += blockDim.x) {
                 int s = pr / a.k, kk = pr - s * a.k;
-                dz[pr] = dot_chain(W[a.k * a.d + kk],  // bias
-                                   W + kk * a.d, xb + s * a.d, a.d);
+                const float* wk = W + kk * a.d;
+                const float* xs = xb + s * a.d;
+                float bias = W[a.k * a.d + kk];
+                if constexpr (PIPE) dz[pr] = dot_chain_pipe(bias, wk, xs, a.d);
+                else dz[pr] = dot_chain(bias, wk, xs, a.d);
             }
             __syncthreads();
             // dLoss/dz of sample s with label y, in place over the sample's
@@ -347,6 +480,12 @@ DEV_INLINE void logreg_update(const LogregArgs& a, int node, int c, float* W,
             // dz = (p - 1_y)/m * a*(1-a)
             auto dz_row = [&](int s, float y) __attribute__((always_inline)) {
                 float* zs = dz + s * a.k;
+                if constexpr (PIPE) {
+                    if (a.k == 2) {  // the binary row stays in registers
+                        dz_row_regs<2>(zs, y, m);
+                        return;
+                    }
+                }
                 float amax = -1e30f;
                 for (int kk = 0; kk < a.k; ++kk) {
                     float sg = 1.0f / (1.0f + __expf(-zs[kk]));
@@ -374,12 +513,16 @@ DEV_INLINE void logreg_update(const LogregArgs& a, int node, int c, float* W,
             // SGD step (thread = parameter)
             for (int e = tid; e < a.k * a.d; e += blockDim.x) {
                 int kk = e / a.d, dd = e - kk * a.d;
-                float g = col_chain(dz + kk, a.k, xb + dd, a.d, m);
+                float g = PIPE
+                    ? col_chain_exact<true>(dz + kk, a.k, xb + dd, a.d, m)
+                    : col_chain(dz + kk, a.k, xb + dd, a.d, m);
                 if (a.wd != 0.f) g += a.wd * W[e];
                 W[e] -= a.lr * g;
             }
             for (int e = tid; e < a.k; e += blockDim.x) {
-                float g = col_chain(dz + e, a.k, nullptr, 0, m);
+                float g = PIPE
+                    ? col_chain_exact<false>(dz + e, a.k, nullptr, 0, m)
+                    : col_chain(dz + e, a.k, nullptr, 0, m);
                 W[a.k * a.d + e] -= a.lr * g;
             }
             __syncthreads();
@@ -391,7 +534,7 @@ DEV_INLINE void logreg_update(const LogregArgs& a, int node, int c, float* W,
 // LIM = limited merge: every mean merge below becomes lim_rule on the two
 // ages at that point. The plain instantiation compiles to the mean-merge
 // code unchanged.
-template <bool LIM, bool BIG = false>
+template <bool LIM, bool BIG = false, bool PIPE = false>
 DEV_INLINE void logreg_process_node(const LogregArgs& a, int i)
 {
     int node = a.nodes[i];
@@ -459,7 +602,7 @@ DEV_INLINE void logreg_process_node(const LogregArgs& a, int i)
             }
         };
         issue_pre(j0 + 1);
-        logreg_update<BIG>(a, node, c, W, xb, dz, age, /*prestaged=*/1);
+        logreg_update<BIG, PIPE>(a, node, c, W, xb, dz, age, /*prestaged=*/1);
         int rs0 = a.rslots ? a.rslots[j0] : -1;
         if (rs0 >= 0) {  // first delivery's PUSH_PULL reply snapshot
             copy_row(a.slots + (long)rs0 * a.D, W, a.D);
@@ -502,7 +645,7 @@ DEV_INLINE void logreg_process_node(const LogregArgs& a, int i)
                 age = max(age, pre_age);
                 __syncthreads();
                 issue_pre(j + 1);
-                logreg_update<BIG>(a, node, c, W, xb, dz, age, /*prestaged=*/xb_keep);
+                logreg_update<BIG, PIPE>(a, node, c, W, xb, dz, age, /*prestaged=*/xb_keep);
             } else {  // PASS (pass-through coin resolved to adopt)
                 copy_row(W, srow2, a.D);
                 age = a.slot_ages[slot2];
@@ -527,7 +670,7 @@ DEV_INLINE void logreg_process_node(const LogregArgs& a, int i)
     int age = a.ages[node];
 
     if (a.update_only) {
-        logreg_update<BIG>(a, node, c, W, xb, dz, age);
+        logreg_update<BIG, PIPE>(a, node, c, W, xb, dz, age);
     } else {
         for (int j = a.ptr[i]; j < a.ptr[i + 1]; ++j) {
             int slot = a.dslots[j];
@@ -546,19 +689,19 @@ DEV_INLINE void logreg_process_node(const LogregArgs& a, int i)
                 }
                 age = max(age, sage);
                 __syncthreads();
-                logreg_update<BIG>(a, node, c, W, xb, dz, age);
+                logreg_update<BIG, PIPE>(a, node, c, W, xb, dz, age);
             } else if (md == MODE_UPDATE) {
                 // adopt the received model, then train it
                 copy_row(W, srow, a.D);
                 age = sage;
                 __syncthreads();
-                logreg_update<BIG>(a, node, c, W, xb, dz, age);
+                logreg_update<BIG, PIPE>(a, node, c, W, xb, dz, age);
             } else if (md == MODE_UPDATE_MERGE) {
-                logreg_update<BIG>(a, node, c, W, xb, dz, age);
+                logreg_update<BIG, PIPE>(a, node, c, W, xb, dz, age);
                 copy_row(W2, srow, a.D);
                 __syncthreads();
                 int age2 = sage;
-                logreg_update<BIG>(a, node, c, W2, xb, dz, age2);
+                logreg_update<BIG, PIPE>(a, node, c, W2, xb, dz, age2);
                 if constexpr (LIM) {
                     // the rule sees the two post-training ages
                     lim_merge_row(lim_rule(age, age2, a.lim), W, W2, a.D);
@@ -611,6 +754,32 @@ __global__ void __launch_bounds__(128)
 tick_logreg_lim_big_kernel(LogregArgs a)
 {
     logreg_process_node<true, true>(a, blockIdx.x);
+}
+
+// the same four for thin launches (Plan::thin_rows): the pipelined update,
+// whose registers cost no occupancy while every wave has a SIMD to itself
+__global__ void __launch_bounds__(128)
+tick_logreg_thin_kernel(LogregArgs a)
+{
+    logreg_process_node<false, false, true>(a, blockIdx.x);
+}
+
+__global__ void __launch_bounds__(128)
+tick_logreg_lim_thin_kernel(LogregArgs a)
+{
+    logreg_process_node<true, false, true>(a, blockIdx.x);
+}
+
+__global__ void __launch_bounds__(128)
+tick_logreg_big_thin_kernel(LogregArgs a)
+{
+    logreg_process_node<false, true, true>(a, blockIdx.x);
+}
+
+__global__ void __launch_bounds__(128)
+tick_logreg_lim_big_thin_kernel(LogregArgs a)
+{
+    logreg_process_node<true, true, true>(a, blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------
@@ -2541,10 +2710,20 @@ template <typename Args>
 struct Plan {
     Args a{};
     void (*kernel)(Args) = nullptr;
+    // a second instantiation for launches of at most thin_rows workgroups,
+    // or null (see thin_launch_rows)
+    void (*kernel_thin)(Args) = nullptr;
+    int thin_rows = 0;
     size_t smem = 0;
     int threads = 0;
     SnapGeom snap{};
 };
+
+template <typename Args>
+static auto plan_kernel(const Plan<Args>& L, int n)
+{
+    return (L.kernel_thin && n <= L.thin_rows) ? L.kernel_thin : L.kernel;
+}
 
 // the per-delivery channel of a family: a `const int*` member of its args
 template <typename Args>
@@ -2598,6 +2777,22 @@ static bool big_batch(int64_t bs, int Smax)
     return batch_rows(bs, Smax) > LOGREG_THREADS;
 }
 
+// The largest launch whose waves each have a SIMD to themselves (4 SIMDs per
+// CU): up to there a kernel's register count costs no occupancy, so the
+// instantiation with the shorter dependent chain and more registers runs;
+// above it the one that keeps 8 waves per SIMD.
+static int thin_launch_rows(int threads)
+{
+    int dev = 0, cus = 0;
+    hipError_t err = hipGetDevice(&dev);
+    if (err == hipSuccess)
+        err = hipDeviceGetAttribute(
+            &cus, hipDeviceAttributeMultiprocessorCount, dev);
+    TORCH_CHECK(err == hipSuccess, "device query failed: ",
+                hipGetErrorString(err));
+    return cus * 4 / std::max(1, threads / WAVE);
+}
+
 // merge_limit of a plan: -1 = plain mean merge, L >= 0 = limited merge.
 // Ages are int32 and the rule adds L to one, so L is kept far below 2^31.
 static int check_merge_limit(int64_t merge_limit)
@@ -2627,13 +2822,18 @@ static Plan<LogregArgs> logreg_plan(
     int bsmax = batch_rows(bs, a.Smax);
     L.smem = sizeof(float) * (2 * a.D + (size_t)bsmax * a.d + (size_t)bsmax * a.k);
     TORCH_CHECK(L.smem <= 160 * 1024, "logreg LDS budget exceeded: ", L.smem);
-    if (big_batch(bs, a.Smax))
-        L.kernel = (merge_limit >= 0) ? tick_logreg_lim_big_kernel
-                                      : tick_logreg_big_kernel;
-    else
-        L.kernel = (merge_limit >= 0) ? tick_logreg_lim_kernel
-                                      : tick_logreg_kernel;
+    bool lim = merge_limit >= 0;
+    if (big_batch(bs, a.Smax)) {
+        L.kernel = lim ? tick_logreg_lim_big_kernel : tick_logreg_big_kernel;
+        L.kernel_thin = lim ? tick_logreg_lim_big_thin_kernel
+                            : tick_logreg_big_thin_kernel;
+    } else {
+        L.kernel = lim ? tick_logreg_lim_kernel : tick_logreg_kernel;
+        L.kernel_thin = lim ? tick_logreg_lim_thin_kernel
+                            : tick_logreg_thin_kernel;
+    }
     L.threads = LOGREG_THREADS;
+    L.thin_rows = thin_launch_rows(LOGREG_THREADS);
     L.snap = {a.D, a.D, 0, 1};
     return L;
 }
@@ -2886,7 +3086,8 @@ static void launch_tick(Plan<Args>& L, const TickEvents& ev, bool update_only,
     e.dslots = iptr(ev.del_slots); e.rslots = iptr(ev.reply_slots);
     e.update_only = update_only;
     if (chan) L.a.*chan = iptr(chan_vals);
-    launch_kernel(L.kernel, n, L.threads, L.smem, current_stream(), L.a);
+    launch_kernel(plan_kernel(L, n), n, L.threads, L.smem, current_stream(),
+                  L.a);
 }
 
 // `merge_limit` of the logreg and MLP entry points is the limited-merge
@@ -3073,7 +3274,7 @@ static void stream_round(Plan<Args>& L, const RoundArrays& r,
                        const int* dslots, const int* rslots, const int* pids) {
         e.nodes = nodes; e.ptr = nptr; e.dslots = dslots; e.rslots = rslots;
         if (chan) L.a.*chan = pids;
-        launch_kernel(L.kernel, n, L.threads, L.smem, s, L.a);
+        launch_kernel(plan_kernel(L, n), n, L.threads, L.smem, s, L.a);
     };
     const int* const* a = r.dev;
     for (int t = 0; t < r.delta; ++t) {
@@ -3472,11 +3673,17 @@ torch::Tensor eval_metrics_scores(torch::Tensor scores, torch::Tensor Y,
 // schedule becomes a Python object.
 //
 // Ownership: the driver owns a ring of RD_RING upload slots (pinned host
-// buffer + device buffer + event) and two metric staging buffers (pinned
-// host + event). A slot's event is recorded after the last work of its
-// round that reads the slot; the slot is rewritten, grown or freed only
-// after that event completed. The state, pool and eval tensors are held by
-// reference; the pool is replaced through set_pool() when it grows.
+// buffer + device buffer + event) and two metric stages (pinned host
+// staging + event, and with eval_overlap a device buffer of gathered params
+// rows + the gather's event). A slot's event is recorded after the last
+// work of its round that reads the slot; the slot is rewritten, grown or
+// freed only after that event completed. At most two evaluations are in
+// flight and the older one is collected, which waits for its event, before
+// a third is launched: that frees a stage, staging and gathered rows alike,
+// before it is reused. A held round has launched nothing, so the rule holds
+// across its retry; a failed step drains both side streams. The state, pool
+// and eval tensors are held by reference; the pool is replaced through
+// set_pool() when it grows.
 //
 // Two measured options, both on by default (profiles/round_driver.md):
 // mapped_metrics: the eval kernel writes its [R, 5] rows straight into the
@@ -3485,6 +3692,13 @@ torch::Tensor eval_metrics_scores(torch::Tensor scores, torch::Tensor Y,
 // side_upload: the H2D copy runs on a stream of the driver's own and the
 //   compute stream waits for its event, which takes the copy off the
 //   kernels' chain.
+// One more, off by default: it gained 2 % on the flagship line, inside that
+// line's spread (profiles/round_chain.md):
+// eval_overlap: a sampled evaluation's rows are gathered on the compute
+//   stream by the snapshot kernel and the eval kernel runs on a third
+//   stream over that copy, beside the next round's first launches (off, or
+//   with no sampled ids: the eval kernel runs in the compute stream and
+//   reads params).
 // ---------------------------------------------------------------------------
 
 #define RD_CHECK(expr)                                                     \
@@ -3546,10 +3760,11 @@ public:
                 torch::Tensor slot_ages, torch::Tensor X, torch::Tensor Y,
                 torch::Tensor counts, torch::Tensor gx, torch::Tensor gy,
                 const std::string& family, py::tuple plan, py::capsule source,
-                bool eval_all, bool mapped_metrics, bool side_upload)
+                bool eval_all, bool mapped_metrics, bool side_upload,
+                bool eval_overlap)
         : st_{params, ages, slots, slot_ages, X, Y, counts}, gx_(gx), gy_(gy),
           source_cap_(source), eval_all_(eval_all), mapped_(mapped_metrics),
-          side_upload_(side_upload)
+          side_upload_(side_upload), eval_overlap_(eval_overlap)
     {
         TORCH_CHECK(std::string(source.name() ? source.name() : "") ==
                         "gossipy_amd.RoundSource",
@@ -3614,6 +3829,13 @@ public:
                                                   hipStreamNonBlocking));
                 ++rd_live[RD_STREAM];
                 rd_event_create(&up_ev_);
+            }
+            if (eval_overlap_) {
+                RD_CHECK(hipStreamCreateWithFlags(&ev_stream_,
+                                                  hipStreamNonBlocking));
+                ++rd_live[RD_STREAM];
+                for (auto& m : stage_)
+                    rd_event_create(&m.gev);
             }
         } catch (...) {
             release();
@@ -3738,6 +3960,9 @@ private:
         float* h_dev = nullptr;  // its device address
         size_t cap_rows = 0;
         hipEvent_t ev = nullptr;
+        float* rows_d = nullptr;  // gathered params rows [rows_cap, D]
+        size_t rows_cap = 0;
+        hipEvent_t gev = nullptr;  // the gather into rows_d is done
         int64_t round = 0;
         int64_t rows = 0;
     };
@@ -3810,6 +4035,32 @@ private:
         m.cap_rows = cap;
     }
 
+    // The stage's gathered-rows buffer and the identity index array for
+    // `rows` rows. The stage is free (see the ownership comment), so nothing
+    // reads its old buffer; the identity array may still be read by the
+    // other stage's gather, which the compute stream is drained of first.
+    void grow_gather(Stage& m, size_t rows, hipStream_t s)
+    {
+        size_t cap = grown_capacity(m.rows_cap, rows);
+        if (cap != m.rows_cap) {
+            if (m.rows_d) RD_CHECK(rd_dev_free(m.rows_d));
+            m.rows_d = nullptr; m.rows_cap = 0;
+            rd_dev_alloc((void**)&m.rows_d, cap * ev_.D * sizeof(float));
+            m.rows_cap = cap;
+        }
+        if (cap > ident_cap_) {
+            RD_CHECK(hipStreamSynchronize(s));
+            if (ident_d_) RD_CHECK(rd_dev_free(ident_d_));
+            ident_d_ = nullptr; ident_cap_ = 0;
+            rd_dev_alloc((void**)&ident_d_, cap * sizeof(int));
+            std::vector<int> iota(cap);
+            for (size_t i = 0; i < cap; ++i) iota[i] = (int)i;
+            RD_CHECK(hipMemcpy(ident_d_, iota.data(), cap * sizeof(int),
+                               hipMemcpyHostToDevice));
+            ident_cap_ = cap;
+        }
+    }
+
     // enqueue the held round; returns the rows its evaluation will have
     int64_t run_held()
     {
@@ -3880,22 +4131,45 @@ private:
                 EvalArgs a = ev_;
                 a.nodes = lay.n_eval ? sl.d + lay.eval_off : nullptr;
                 a.out = mapped_ ? m.h_dev : d_out_;
+                hipStream_t es = s;
+                if (eval_overlap_ && lay.n_eval) {
+                    // sampled evaluation leaves the compute stream: its
+                    // rows are gathered here, behind the round's kernels,
+                    // and the eval kernel reads the copy on its own stream
+                    // while the next round rewrites params
+                    grow_gather(m, (size_t)rows, s);
+                    launch_snap(ev_.params, nullptr, m.rows_d, nullptr,
+                                a.nodes, ident_d_, (int)rows,
+                                SnapGeom{ev_.D, ev_.D, 0, 0}, s);
+                    RD_CHECK(hipGetLastError());
+                    RD_CHECK(hipEventRecord(m.gev, s));
+                    // the gather is the last reader of the upload slot
+                    RD_CHECK(hipEventRecord(sl.ev, s));
+                    recorded = true;
+                    es = ev_stream_;
+                    RD_CHECK(hipStreamWaitEvent(es, m.gev, 0));
+                    a.params = m.rows_d;
+                    a.nodes = nullptr;  // row i is node i
+                }
                 launch_kernel(eval_metrics_kernel, (int)rows, 256, ev_smem_,
-                              s, a);
+                              es, a);
                 if (!mapped_)
                     RD_CHECK(hipMemcpyAsync(m.h, d_out_,
                                             (size_t)rows * 5 * sizeof(float),
-                                            hipMemcpyDeviceToHost, s));
-                RD_CHECK(hipEventRecord(m.ev, s));
+                                            hipMemcpyDeviceToHost, es));
+                RD_CHECK(hipEventRecord(m.ev, es));
                 m.round = held_r_; m.rows = rows;
                 pending_.push_back(mi);
                 stage_next_ ^= 1;
             }
-            // after the eval launch: it reads its ids from this slot
-            RD_CHECK(hipEventRecord(sl.ev, s));
+            // after the eval launch: in-stream, it reads its ids from this
+            // slot
+            if (!recorded) RD_CHECK(hipEventRecord(sl.ev, s));
             recorded = true;
             return rows;
         } catch (...) {
+            // a stage that was launched but not queued must not run on
+            if (ev_stream_) (void)hipStreamSynchronize(ev_stream_);
             if (!recorded) {
                 // what was enqueued may still read the slot: drain it
                 // before the slot counts as free again
@@ -3915,11 +4189,24 @@ private:
             if (s.d) (void)rd_dev_free(s.d);
             s = Slot{};
         }
+        if (ev_stream_) (void)hipStreamSynchronize(ev_stream_);
         for (auto& m : stage_) {
             if (m.ev) { (void)hipEventSynchronize(m.ev); rd_event_destroy(m.ev); }
+            if (m.gev) {
+                (void)hipEventSynchronize(m.gev);
+                rd_event_destroy(m.gev);
+            }
             if (m.h) (void)rd_host_free(m.h);
+            if (m.rows_d) (void)rd_dev_free(m.rows_d);
             m = Stage{};
         }
+        if (ident_d_) (void)rd_dev_free(ident_d_);
+        ident_d_ = nullptr; ident_cap_ = 0;
+        if (ev_stream_) {
+            (void)hipStreamDestroy(ev_stream_);
+            --rd_live[RD_STREAM];
+        }
+        ev_stream_ = nullptr;
         if (d_out_) (void)rd_dev_free(d_out_);
         d_out_ = nullptr;
         if (up_ev_) rd_event_destroy(up_ev_);
@@ -3935,7 +4222,7 @@ private:
     torch::Tensor gx_, gy_;
     py::capsule source_cap_;
     RoundSource src_{};
-    bool eval_all_, mapped_, side_upload_;
+    bool eval_all_, mapped_, side_upload_, eval_overlap_;
     bool linear_ = false;
     Plan<LogregArgs> lg_;
     Plan<LinearArgs> ln_;
@@ -3958,6 +4245,9 @@ private:
     size_t d_out_rows_ = 0;
     hipStream_t up_stream_ = nullptr;
     hipEvent_t up_ev_ = nullptr;
+    hipStream_t ev_stream_ = nullptr;  // eval_overlap: the eval kernels
+    int* ident_d_ = nullptr;           // 0, 1, 2, ...: the gather's slot ids
+    size_t ident_cap_ = 0;
 };
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
@@ -3967,13 +4257,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
                       torch::Tensor, torch::Tensor, torch::Tensor,
                       torch::Tensor, torch::Tensor, torch::Tensor,
                       const std::string&, py::tuple, py::capsule, bool, bool,
-                      bool>(),
+                      bool, bool>(),
              py::arg("params"), py::arg("ages"), py::arg("slots"),
              py::arg("slot_ages"), py::arg("X"), py::arg("Y"),
              py::arg("counts"), py::arg("gx"), py::arg("gy"),
              py::arg("family"), py::arg("plan"), py::arg("source"),
              py::arg("eval_all") = false, py::arg("mapped_metrics") = true,
-             py::arg("side_upload") = true)
+             py::arg("side_upload") = true, py::arg("eval_overlap") = false)
         .def("step", &RoundDriver::step)
         .def("set_pool", &RoundDriver::set_pool)
         .def("poll_eval", &RoundDriver::poll_eval)
