@@ -8,9 +8,10 @@ unavailable offline); this runs the same protocol on a rotated synthetic
 task with a TorchMLP — the non-IID structure (two client groups with
 feature-rotated distributions) is preserved.
 
-``--engine`` runs the batched MI355X PENS instead (logreg family, device
--side candidate scoring + top-m merges, one host sync at the step
-boundary).
+``--engine`` runs the batched MI355X PENS instead (device-side candidate
+scoring + top-m merges, one host sync at the step boundary). ``--model``
+picks its family: ``logreg`` (the default) or ``mlp``, the object-layer
+half's ``TorchMLP(d, 2, (32,))`` as an ``MLPSpec``.
 """
 
 import os
@@ -39,6 +40,9 @@ def main():
     ap.add_argument("--rounds", type=int, default=30)
     ap.add_argument("--engine", action="store_true",
                     help="batched MI355X PENS instead of the object layer")
+    ap.add_argument("--model", choices=("logreg", "mlp"), default="logreg",
+                    help="with --engine: the model family (mlp = the"
+                         " object-layer half's one-hidden-layer MLP)")
     ap.add_argument("--engine-cnn", action="store_true",
                     help="batched engine with the reference CIFAR10Net CNN"
                          " (TorchModuleSpec; convs on MIOpen)")
@@ -107,11 +111,16 @@ def main_engine(args):
         DataArena,
         EngineConfig,
         LogRegSpec,
+        MLPSpec,
     )
     from gossipy_amd.simul import SimulationReport
 
     device = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
     n, d = args.nodes, 20
+    if args.model == "mlp":
+        spec = MLPSpec(d_in=d, n_classes=2, hidden=(32,), lr=0.1)
+    else:
+        spec = LogRegSpec(d_in=d, n_classes=2, lr=0.1)
     X, y = make_synthetic_classification((50 * n, d, 2), seed=42, margin=2.0)
     idx = np.random.default_rng(42).permutation(len(y))
     cut = int(0.9 * len(y))
@@ -121,10 +130,10 @@ def main_engine(args):
     )
     cfg = EngineConfig(
         n_nodes=n, delta=100, protocol=AntiEntropyProtocol.PUSH,
-        model_size=2 * d + 2, sampling_eval=0.25, seed=42,
+        model_size=spec.D, sampling_eval=0.25, seed=42,
     )
     sim = BatchedPENSGossipSimulator(
-        cfg, LogRegSpec(d_in=d, n_classes=2, lr=0.1), data,
+        cfg, spec, data,
         n_sampled=6, m_top=2, step1_rounds=max(2, args.rounds // 3),
         device=device,
     )

@@ -1177,10 +1177,10 @@ class TorchBackend:
         gossipy/model/handler.py:260-280) and bump the winner counters
         (gossipy/node.py:771-782). ``counts`` is ``[n_local, n_nodes]``
         int32 (device-resident on the HIP backend). logreg scores each
-        candidate with one affine map; torchmod (the Onoszko CNN) runs a
-        node-batched vmap forward over the candidate rows."""
-        assert spec.family in ("logreg", "torchmod"), (
-            "PENS engine path: logreg or torchmod family"
+        candidate with one affine map; mlp and torchmod (the Onoszko CNN)
+        run a node-batched forward over the candidate rows."""
+        assert spec.family in ("logreg", "mlp", "torchmod"), (
+            "PENS engine path: logreg, mlp or torchmod family"
         )
         ptr = pens_ptr.tolist()
         for i, node_t in enumerate(pens_nodes.tolist()):
@@ -1214,15 +1214,19 @@ class TorchBackend:
                 pred = (x @ W.t() + b).argmax(dim=1)
                 accs.append(float((pred == y).float().mean()))
             return accs
-        # torchmod: one vmap forward over the m candidate rows
+        # mlp / torchmod: one node-batched forward over the m candidate
+        # rows (bmm per layer / vmap), the slot pool standing in for the
+        # arena
         from types import SimpleNamespace
 
         slots_t = torch.tensor(cands, dtype=torch.long,
                                device=pool.slots.device)
         state = SimpleNamespace(params=pool.slots)
-        sc = self.torchmod_scores(
-            state, spec, slots_t, x
-        )  # [m, c, k]
+        if spec.family == "mlp":
+            sc = self.scores(state, spec, slots_t, x)
+        else:
+            sc = self.torchmod_scores(state, spec, slots_t, x)
+        # sc: [m, c, k]
         pred = sc.argmax(dim=2)
         return (pred == y.unsqueeze(0)).float().mean(dim=1).tolist()
 
@@ -1481,9 +1485,20 @@ class HIPBackend(TorchBackend):
                 pens_slots, pens_owners, counts, m_top,
             )
             return
-        assert spec.family == "logreg", "PENS engine path: logreg family"
+        assert spec.family in ("logreg", "mlp"), (
+            "PENS engine path: logreg or mlp family"
+        )
+        # the kernels keep per-candidate tallies in a fixed LDS array;
+        # pens_ptr is a host tensor here, so the check costs no sync
+        max_cand = int(self.ext.PENS_MAX_CAND)
+        n_cand = int(pens_ptr.diff().max())
+        if n_cand > max_cand:
+            raise ValueError(
+                f"a PENS event has {n_cand} candidates; the HIP kernels"
+                f" score at most {max_cand} per event (lower n_sampled)"
+            )
         dev = state.params.device
-        self.ext.tick_pens(
+        events = (
             state.params,
             state.ages,
             pool.slots,
@@ -1496,14 +1511,23 @@ class HIPBackend(TorchBackend):
             data.x,
             data.y,
             data.counts,
-            spec.d_in,
-            spec.n_classes,
+        )
+        sgd = (
             m_top,
             spec.lr,
             spec.weight_decay,
             max(1, spec.local_epochs),
             spec.batch_size,
         )
+        if spec.family == "mlp":
+            self.ext.tick_pens_mlp(
+                *events,
+                self._mlp_layout(spec, dev),
+                len(spec.layer_offsets()),
+                *sgd,
+            )
+        else:
+            self.ext.tick_pens(*events, spec.d_in, spec.n_classes, *sgd)
 
     def eval_local_fast(self, state, spec, local_ids, tx, ty, tcounts):
         """Per-node test-shard evaluation (the reference's ``evaluate``

@@ -1831,9 +1831,13 @@ class BatchedPENSGossipSimulator(BatchedGossipSimulator):
     winner counts accumulated device-side; the only host<->device
     dependency is ONE counts read at the step boundary, where
     ``best_nodes`` is computed and the scheduler's step-2 peer draws are
-    restricted to it. PUSH + MERGE_UPDATE; logreg scores candidates
-    in-kernel (tick_pens), torchmod (the Onoszko CIFAR10Net CNN) scores
-    them with a node-batched vmap forward.
+    restricted to it. PUSH + MERGE_UPDATE. Families: logreg and mlp score
+    candidates in-kernel (tick_pens, tick_pens_mlp — the latter a
+    forward-only MFMA chain per candidate), torchmod (the Onoszko
+    CIFAR10Net CNN) scores them with a node-batched vmap forward. An
+    ``MLPSpec`` must be whole-model (no ``n_parts``, no ``sample_size``):
+    PENS merges whole models by plain mean. Step 2 is plain gossip and runs
+    through the family's tick kernel.
     """
 
     def __init__(
@@ -1850,6 +1854,15 @@ class BatchedPENSGossipSimulator(BatchedGossipSimulator):
             raise ValueError(
                 "PENS merges the top-m candidates by plain mean; a spec with"
                 " age_diff_threshold (limited merge) cannot be used"
+            )
+        if getattr(spec, "family", None) == "mlp" and (
+            getattr(spec, "n_parts", 0) > 0
+            or getattr(spec, "sample_size", 0) > 0
+        ):
+            raise ValueError(
+                "PENS merges whole models by plain mean; an MLPSpec with"
+                " n_parts or sample_size (partitioned / sampled gossip)"
+                " cannot be used"
             )
         super().__init__(cfg, spec, data, device=device)
         from ..core import CreateModelMode

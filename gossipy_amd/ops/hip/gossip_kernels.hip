@@ -30,6 +30,12 @@
 //                           (LimitedMergeMixin._merge,
 //                           gossipy/model/handler.py:690-715) in place of
 //                           the mean; see lim_rule.
+//   tick_pens_kernel, tick_pens_mlp_kernel
+//                         — PENS step-1 events (gossipy/node.py:767-782) for
+//                           logreg / the MLP: score the cached candidates on
+//                           the receiver's shard (the MLP one forward-only on
+//                           mlp_update's MFMA stage, mlp_forward), merge the
+//                           top-m, run the local update.
 //   tick_logreg_big_kernel, tick_logreg_lim_big_kernel, <BIG = true>
 //                         — the logreg kernels for batches of more rows
 //                           than their 128 threads (full-shard batches of
@@ -1602,6 +1608,58 @@ DEV_INLINE f32x4_t mfma_kloop(int Kdim, LoadA la, LoadB lb)
     return acc;
 }
 
+// Forward pass H = X · Wᵀ + b of every layer over the m rows staged at act
+// (ReLU between layers, raw head), on MFMA. The activations are laid out
+// layer after layer behind the input: act[l] is [m, out_l]. Returns the
+// head's [m, k] activations. The caller's barrier must stand between the
+// staging of the input (and of W) and this call; a barrier follows each
+// layer.
+DEV_INLINE float* mlp_forward(const MlpArgs& a, const float* W, float* act,
+                              int m)
+{
+    const int tid = threadIdx.x;
+    const int wave = tid >> 6;
+    const int lane = tid & 63;
+    const int fr = lane & 15;       // A-row / B-col fragment index
+    const int fk = lane >> 4;       // K fragment index (0..3)
+    const int nwaves = blockDim.x >> 6;
+    float* cur = act;
+    float* nxt = act + m * a.d_in;
+    for (int l = 0; l < a.n_layers; ++l) {
+        int w_off = a.layout[4 * l], b_off = a.layout[4 * l + 1];
+        int fin = a.layout[4 * l + 2], fout = a.layout[4 * l + 3];
+        int m16 = (m + 15) >> 4, o16 = (fout + 15) >> 4;
+        for (int tile = wave; tile < m16 * o16; tile += nwaves) {
+            int tr = (tile / o16) << 4, tc = (tile % o16) << 4;
+            f32x4_t acc = mfma_kloop(
+                fin,
+                [&](int k0) {
+                    int q = k0 + fk;
+                    return (tr + fr < m && q < fin)
+                               ? cur[(tr + fr) * fin + q] : 0.f;
+                },
+                [&](int k0) {
+                    int q = k0 + fk;
+                    return (tc + fr < fout && q < fin)
+                               ? W[w_off + (tc + fr) * fin + q]
+                               : 0.f;
+                });
+            for (int r = 0; r < 4; ++r) {
+                int row = tr + (fk << 2) + r, col = tc + fr;
+                if (row < m && col < fout) {
+                    float v = acc[r] + W[b_off + col];
+                    if (l < a.n_layers - 1) v = fmaxf(v, 0.f);  // ReLU
+                    nxt[row * fout + col] = v;
+                }
+            }
+        }
+        __syncthreads();
+        cur = nxt;
+        nxt = nxt + m * fout;
+    }
+    return cur;
+}
+
 // PART = partitioned gossip (PartitionedTMH._local_step + _adjust_gradient,
 // gossipy/model/handler.py:503-520): the age is the LDS vector agev[P],
 // bumped whole before each minibatch step, and every parameter's gradient
@@ -1641,40 +1699,7 @@ DEV_INLINE void mlp_update(const MlpArgs& a, int node, float* W,
             }
             __syncthreads();
             // ---- forward: H = X · Wᵀ + b on MFMA
-            float* cur = in;
-            float* nxt = act + m * a.d_in;
-            for (int l = 0; l < a.n_layers; ++l) {
-                int w_off = a.layout[4 * l], b_off = a.layout[4 * l + 1];
-                int fin = a.layout[4 * l + 2], fout = a.layout[4 * l + 3];
-                int m16 = (m + 15) >> 4, o16 = (fout + 15) >> 4;
-                for (int tile = wave; tile < m16 * o16; tile += nwaves) {
-                    int tr = (tile / o16) << 4, tc = (tile % o16) << 4;
-                    f32x4_t acc = mfma_kloop(
-                        fin,
-                        [&](int k0) {
-                            int q = k0 + fk;
-                            return (tr + fr < m && q < fin)
-                                       ? cur[(tr + fr) * fin + q] : 0.f;
-                        },
-                        [&](int k0) {
-                            int q = k0 + fk;
-                            return (tc + fr < fout && q < fin)
-                                       ? W[w_off + (tc + fr) * fin + q]
-                                       : 0.f;
-                        });
-                    for (int r = 0; r < 4; ++r) {
-                        int row = tr + (fk << 2) + r, col = tc + fr;
-                        if (row < m && col < fout) {
-                            float v = acc[r] + W[b_off + col];
-                            if (l < a.n_layers - 1) v = fmaxf(v, 0.f);  // ReLU
-                            nxt[row * fout + col] = v;
-                        }
-                    }
-                }
-                __syncthreads();
-                cur = nxt;
-                nxt = nxt + m * fout;
-            }
+            float* cur = mlp_forward(a, W, act, m);
             // ---- output grad: softmax-CE on the raw head
             int k = a.layout[4 * (a.n_layers - 1) + 3];
             float* gcur = grad;  // [m, k] for the head, reused per layer
@@ -2302,6 +2327,27 @@ struct PensArgs {
     int epochs, bs;
 };
 
+// Top-min(m_top, n_cand) candidates by correct count, stable in arrival
+// order (the first of equal counts wins): marks them in sel[] and bumps the
+// receiver's winner counter of each one's sender. One thread runs it.
+DEV_INLINE void pens_select(const int* correct, int* sel, int n_cand,
+                            int m_top, int* counts_row, const int* owners)
+{
+    for (int c = 0; c < n_cand; ++c) sel[c] = 0;
+    int m = min(m_top, n_cand);
+    for (int pick = 0; pick < m; ++pick) {
+        int best_c = -1, best_v = -1;
+        for (int c = 0; c < n_cand; ++c) {
+            if (!sel[c] && correct[c] > best_v) {
+                best_v = correct[c];
+                best_c = c;
+            }
+        }
+        sel[best_c] = 1;
+        atomicAdd(&counts_row[owners[best_c]], 1);
+    }
+}
+
 template <bool BIG>  // as logreg_update's
 __global__ void __launch_bounds__(128)
 tick_pens_kernel(PensArgs a)
@@ -2346,21 +2392,9 @@ tick_pens_kernel(PensArgs a)
     __syncthreads();
 
     // --- stable top-m selection (thread 0; n_cand small)
-    if (tid == 0) {
-        for (int c = 0; c < n_cand; ++c) sel[c] = 0;
-        int m = min(a.m_top, n_cand);
-        for (int pick = 0; pick < m; ++pick) {
-            int best_c = -1, best_v = -1;
-            for (int c = 0; c < n_cand; ++c) {
-                if (!sel[c] && correct[c] > best_v) {
-                    best_v = correct[c];
-                    best_c = c;
-                }
-            }
-            sel[best_c] = 1;
-            atomicAdd(&a.counts[(long)node * a.n_total + a.cowners[lo + best_c]], 1);
-        }
-    }
+    if (tid == 0)
+        pens_select(correct, sel, n_cand, a.m_top,
+                    a.counts + (long)node * a.n_total, a.cowners + lo);
     __syncthreads();
 
     // --- merge: (own + sum selected) / (m+1), age = max
@@ -2386,6 +2420,111 @@ tick_pens_kernel(PensArgs a)
     u.d = a.d; u.k = a.k; u.Smax = a.Smax; u.D = a.D;
     u.lr = a.lr; u.wd = a.wd; u.epochs = a.epochs; u.bs = a.bs;
     logreg_update<BIG>(u, node, c_n, W, xb, dz, age);
+    __syncthreads();
+    for (int e = tid; e < a.D; e += blockDim.x)
+        a.params[(long)node * a.D + e] = W[e];
+    if (tid == 0) a.ages[node] = age;
+}
+
+// PENS step-1 event for the MLP family, on the tick_mlp_kernel structure:
+// model row LDS-resident, activations and two grad buffers behind it. The
+// ONE model slab holds each candidate in turn while it is scored (forward
+// only, mlp_forward over the receiver's shard in mlp_update's minibatch
+// chunks, so the act scratch is large enough), then the own row, onto
+// which the selected candidates are added straight from HBM.
+struct PensMlpArgs {
+    MlpArgs m;              // nodes/ptr: event receivers / candidate ranges
+    const int* cslots;      // candidate slots
+    const int* cowners;     // candidate senders (global node ids)
+    int* wins;              // [n_local, n_total] winner counters
+    int m_top, n_total;
+};
+
+__global__ void __launch_bounds__(512)
+tick_pens_mlp_kernel(PensMlpArgs p)
+{
+    const MlpArgs& a = p.m;
+    int i = blockIdx.x;
+    int node = a.nodes[i];
+    int tid = threadIdx.x;
+    int lo = a.ptr[i], hi = a.ptr[i + 1];
+    int n_cand = hi - lo;
+    extern __shared__ float sm[];
+    float* W = sm;          // D
+    int bsmax = (a.bs == 0) ? a.Smax : min(a.bs, a.Smax);
+    float* act = W + a.D;
+    int act_total = 0;
+    for (int l = 0; l < a.n_layers; ++l) act_total += a.layout[4 * l + 3];
+    float* grad = act + bsmax * (a.d_in + act_total);
+    __shared__ int correct[PENS_MAX_CAND];
+    __shared__ int sel[PENS_MAX_CAND];
+
+    int c_n = a.counts[node];
+    int bsz = (a.bs == 0) ? c_n : min(a.bs, c_n);
+    const float* Xn = a.X + (long)node * a.Smax * a.d_in;
+    const float* Yn = a.Y + (long)node * a.Smax;
+    int k = a.layout[4 * (a.n_layers - 1) + 3];
+
+    // --- score candidates in arrival order
+    for (int c = tid; c < n_cand; c += blockDim.x) correct[c] = 0;
+    for (int c = 0; c < n_cand; ++c) {
+        const float* Wc = a.slots + (long)p.cslots[lo + c] * a.D;
+        for (int e = tid; e < a.D; e += blockDim.x) W[e] = Wc[e];
+        for (int s0 = 0; s0 < c_n; s0 += bsz) {
+            int m = min(bsz, c_n - s0);
+            for (int e = tid; e < m * a.d_in; e += blockDim.x)
+                act[e] = Xn[(long)s0 * a.d_in + e];
+            __syncthreads();
+            const float* head = mlp_forward(a, W, act, m);
+            // (thread = sample, block-strided: a chunk may have more rows
+            // than the block has threads); ascending scan, strict > — the
+            // first maximum wins, as torch.argmax
+            int my = 0;
+            for (int s = tid; s < m; s += blockDim.x) {
+                const float* z = head + s * k;
+                float best = z[0];
+                int bj = 0;
+                for (int kk = 1; kk < k; ++kk) {
+                    if (z[kk] > best) { best = z[kk]; bj = kk; }
+                }
+                if (bj == (int)Yn[s0 + s]) my += 1;
+            }
+            for (int off = WAVE / 2; off > 0; off >>= 1)
+                my += __shfl_down(my, off, WAVE);
+            if ((tid & (WAVE - 1)) == 0 && my) atomicAdd(&correct[c], my);
+            // the head is read out before the next chunk or candidate
+            // overwrites act and W
+            __syncthreads();
+        }
+    }
+    __syncthreads();
+
+    // --- stable top-m selection (thread 0; n_cand small)
+    if (tid == 0)
+        pens_select(correct, sel, n_cand, p.m_top,
+                    p.wins + (long)node * p.n_total, p.cowners + lo);
+    __syncthreads();
+
+    // --- merge: (own + sum selected) / (n_sel+1), age = max; each thread
+    //     owns its elements of W throughout, so no barrier until the end
+    for (int e = tid; e < a.D; e += blockDim.x)
+        W[e] = a.params[(long)node * a.D + e];
+    int n_sel = 0;
+    int age = a.ages[node];
+    for (int c = 0; c < n_cand; ++c) {
+        if (!sel[c]) continue;
+        n_sel += 1;
+        int slot = p.cslots[lo + c];
+        const float* Wc = a.slots + (long)slot * a.D;
+        for (int e = tid; e < a.D; e += blockDim.x) W[e] += Wc[e];
+        age = max(age, a.slot_ages[slot]);
+    }
+    float inv = 1.0f / (n_sel + 1);
+    for (int e = tid; e < a.D; e += blockDim.x) W[e] *= inv;
+    __syncthreads();
+
+    // --- local update
+    mlp_update<false>(a, node, W, act, grad, age);
     __syncthreads();
     for (int e = tid; e < a.D; e += blockDim.x)
         a.params[(long)node * a.D + e] = W[e];
@@ -3587,6 +3726,37 @@ void tick_pens(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
                        a);
 }
 
+void tick_pens_mlp(torch::Tensor params, torch::Tensor ages,
+                   torch::Tensor slots, torch::Tensor slot_ages,
+                   torch::Tensor nodes, torch::Tensor ptr,
+                   torch::Tensor cslots, torch::Tensor cowners,
+                   torch::Tensor counts, torch::Tensor X, torch::Tensor Y,
+                   torch::Tensor dcounts, torch::Tensor layout,
+                   int64_t n_layers, int64_t m_top, double lr, double wd,
+                   int64_t epochs, int64_t bs)
+{
+    CHECK_DEV(counts);
+    int n = nodes.size(0);
+    if (n == 0) return;
+    CHECK_DEV(nodes); CHECK_DEV(ptr); CHECK_DEV(cslots); CHECK_DEV(cowners);
+    PensMlpArgs p{};
+    MlpGeom g = mlp_fill(p.m, {params, ages, slots, slot_ages, X, Y, dcounts},
+                         layout, n_layers, lr, wd, epochs, bs,
+                         MODE_MERGE_UPDATE);
+    p.m.nodes = nodes.data_ptr<int>(); p.m.ptr = ptr.data_ptr<int>();
+    p.cslots = cslots.data_ptr<int>(); p.cowners = cowners.data_ptr<int>();
+    p.wins = counts.data_ptr<int>();
+    p.m_top = m_top; p.n_total = counts.size(1);
+    // LDS: ONE model slab + activations + 2 grad buffers, next to the
+    // kernel's static correct[] / sel[]
+    size_t smem = sizeof(float) * ((size_t)p.m.D + g.scratch);
+    TORCH_CHECK(smem + 2 * sizeof(int) * PENS_MAX_CAND <= 160 * 1024,
+        "pens mlp LDS budget exceeded (", smem,
+        " B of dynamic LDS); shrink batch_size/hidden");
+    launch_kernel(tick_pens_mlp_kernel, n, g.threads, smem, current_stream(),
+                  p);
+}
+
 // Scoring-mode launch geometry from a.D, a.d and a.n_eval: sets a.tile and
 // returns the dynamic LDS.
 // LDS: model + scores + their label-compacted copy + binarized labels
@@ -4324,6 +4494,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           "single-launch cooperative whole-round executor (logreg)");
     m.def("tick_pens", &tick_pens,
           "PENS step-1 event: score candidates, merge top-m, count winners");
+    m.def("tick_pens_mlp", &tick_pens_mlp,
+          "PENS step-1 event, MLP family: MFMA forward scoring of the"
+          " candidates, top-m merge, MLP SGD");
+    // most candidates one PENS event may carry (tick_pens, tick_pens_mlp)
+    m.attr("PENS_MAX_CAND") = PENS_MAX_CAND;
     m.def("eval_metrics", &eval_metrics,
           "fused per-node eval metrics on a shared eval set (K13)");
     m.def("eval_metrics_scores", &eval_metrics_scores,
