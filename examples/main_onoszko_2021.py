@@ -11,7 +11,10 @@ feature-rotated distributions) is preserved.
 ``--engine`` runs the batched MI355X PENS instead (device-side candidate
 scoring + top-m merges, one host sync at the step boundary). ``--model``
 picks its family: ``logreg`` (the default) or ``mlp``, the object-layer
-half's ``TorchMLP(d, 2, (32,))`` as an ``MLPSpec``.
+half's ``TorchMLP(d, 2, (32,))`` as an ``MLPSpec``. ``--local-test`` gives
+the engine run the object-layer half's data: the two rotated client groups
+and a held-out tenth of every node's rows as its own test shard, evaluated
+next to the global set (``final local eval``).
 """
 
 import os
@@ -43,6 +46,11 @@ def main():
     ap.add_argument("--model", choices=("logreg", "mlp"), default="logreg",
                     help="with --engine: the model family (mlp = the"
                          " object-layer half's one-hidden-layer MLP)")
+    ap.add_argument("--local-test", action="store_true",
+                    help="with --engine: the two rotated client groups of"
+                         " the object-layer half, a 90/10 train/test split"
+                         " of every node's rows, and the evaluation on each"
+                         " node's own test shard next to the global one")
     ap.add_argument("--engine-cnn", action="store_true",
                     help="batched engine with the reference CIFAR10Net CNN"
                          " (TorchModuleSpec; convs on MIOpen)")
@@ -51,6 +59,8 @@ def main():
                          " (vmap-scored candidates, top-m merges) instead"
                          " of plain merge-update gossip")
     args = ap.parse_args()
+    if args.local_test and (not args.engine or args.nodes < 2):
+        ap.error("--local-test needs --engine and at least two nodes")
 
     if args.engine_cnn:
         return main_engine_cnn(args)
@@ -124,10 +134,36 @@ def main_engine(args):
     X, y = make_synthetic_classification((50 * n, d, 2), seed=42, margin=2.0)
     idx = np.random.default_rng(42).permutation(len(y))
     cut = int(0.9 * len(y))
-    shards = [(X[s], y[s]) for s in np.array_split(idx[:cut], n)]
-    data = DataArena.from_shards(
-        shards, device, global_eval=(X[idx[cut:]], y[idx[cut:]])
-    )
+    if args.local_test:
+        # the object-layer half's setting: two client groups, the second
+        # one's features rotated, and every node evaluated on a held-out
+        # tenth of its own rows (eval_on_user)
+        rot = torch.from_numpy(
+            np.linalg.qr(np.random.default_rng(7).normal(size=(d, d)))[0]
+        ).float()
+        half = len(X) // 2
+        X = torch.cat([X[:half], X[half:] @ rot])
+        pool = idx[:cut]
+        groups = (pool[pool < half], pool[pool >= half])
+        per_node = [
+            s
+            for g, m in zip(groups, (n // 2, n - n // 2))
+            for s in np.array_split(g, m)
+        ]
+        shards, tests = [], []
+        for s in per_node:
+            c = int(0.9 * len(s))
+            shards.append((X[s[:c]], y[s[:c]]))
+            tests.append((X[s[c:]], y[s[c:]]))
+        data = DataArena.from_shards(
+            shards, device, test_shards=tests,
+            global_eval=(X[idx[cut:]], y[idx[cut:]]),
+        )
+    else:
+        shards = [(X[s], y[s]) for s in np.array_split(idx[:cut], n)]
+        data = DataArena.from_shards(
+            shards, device, global_eval=(X[idx[cut:]], y[idx[cut:]])
+        )
     cfg = EngineConfig(
         n_nodes=n, delta=100, protocol=AntiEntropyProtocol.PUSH,
         model_size=spec.D, sampling_eval=0.25, seed=42,
@@ -141,6 +177,8 @@ def main_engine(args):
     sim.add_receiver(report)
     sim.init_nodes()
     sim.start(n_rounds=args.rounds)
+    if args.local_test:
+        print(f"final local eval: {report.get_evaluation(True)[-1][1]}")
     print(f"final global eval: {report.get_evaluation(False)[-1][1]}")
     n_best = sum(len(b) for b in sim.scheduler.best_nodes or [])
     print(f"selected neighbors across nodes: {n_best}")

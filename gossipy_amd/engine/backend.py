@@ -1534,21 +1534,49 @@ class HIPBackend(TorchBackend):
         on the node's own split, gossipy/node.py:206-224) in ONE launch:
         block r scores node r's model on its own padded shard rows.
         Returns (metric dicts, kept local_ids) skipping empty shards, or
-        ``None`` for families on the generic path."""
-        if spec.family not in ("logreg", "pegasos", "adaline"):
+        ``None`` for families on the generic path.
+
+        The MLP family runs ``eval_mlp`` (MFMA forward + the same metrics
+        epilogue) when ``eval_mlp_tile`` says the model, the shard stride
+        and 16 rows of forward scratch fit the LDS budget, and returns
+        ``None`` otherwise, as under ``GOSSIPY_NO_MLP_EVAL_KERNEL=1`` (A/B
+        runs): the caller's per-node loop serves those. ``eval_mlp`` also
+        has a shared-set mode (empty ``eval_counts``, ``X`` ``[n, d_in]``);
+        it is not wired into :meth:`eval_metrics_fast` /
+        :meth:`eval_metrics_launch`, whose MLP scores still come from
+        :meth:`scores`."""
+        dev = state.params.device
+        if spec.family == "mlp":
+            if os.environ.get("GOSSIPY_NO_MLP_EVAL_KERNEL") == "1":
+                return None
+            dims = spec.dims
+            if spec.n_classes > self.ext.EVAL_KMAX or not self.ext.eval_mlp_tile(
+                state.params.shape[1], spec.d_in, sum(dims[1:]), tx.shape[1]
+            ):
+                return None
+            out = self.ext.eval_mlp(
+                state.params,
+                local_ids.to(dev, torch.int32),
+                tx,
+                ty,
+                self._mlp_layout(spec, dev),
+                len(dims) - 1,
+                tcounts,
+            )
+        elif spec.family in ("logreg", "pegasos", "adaline"):
+            is_margin = spec.family in ("pegasos", "adaline")
+            out = self.ext.eval_metrics(
+                state.params,
+                local_ids.to(dev, torch.int32),
+                tx,
+                ty,
+                spec.d_in,
+                1 if is_margin else spec.n_classes,
+                is_margin,
+                tcounts,
+            )
+        else:
             return None
-        is_margin = spec.family in ("pegasos", "adaline")
-        ids32 = local_ids.to(state.params.device, torch.int32)
-        out = self.ext.eval_metrics(
-            state.params,
-            ids32,
-            tx,
-            ty,
-            spec.d_in,
-            1 if is_margin else spec.n_classes,
-            is_margin,
-            tcounts,
-        )
         vals = out.cpu().numpy()
         res = []
         for row in vals:

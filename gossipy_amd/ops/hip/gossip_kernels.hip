@@ -47,6 +47,12 @@
 //                           more registers; picked host-side for launches
 //                           of at most one wave per SIMD, see
 //                           thin_launch_rows.
+//   eval_metrics_kernel   — K13: accuracy / macro P-R-F1 / pairwise AUC of
+//                           R affine or margin models (or precomputed
+//                           scores) on a shared set or per-node shards.
+//   eval_mlp_kernel       — K13 for the MLP family: mlp_forward over the
+//                           evaluation rows, then eval_metrics_kernel's
+//                           epilogue (eval_epilogue), in one launch.
 //
 // Models are tiny (57x2 logreg ... few-hundred-wide MLPs); per-launch work
 // is launch-latency bound, so kernels are built to let ONE launch cover all
@@ -2102,6 +2108,119 @@ struct EvalArgs {
 
 constexpr int EVAL_KMAX = 16;
 
+// Metrics epilogue shared by eval_metrics_kernel and eval_mlp_kernel: from
+// the block's staged positive-class scores s1[n_e], binarized labels
+// yb[n_e] and kk x kk confusion counts conf, write the 5-float result row
+// (accuracy, macro precision / recall / F1, AUC; AUC -1 for kk > 2). cs is
+// n_e floats of scratch. The caller's barrier stands between the staging
+// and this call.
+DEV_INLINE void eval_epilogue(float* out_row, int n_e, int kk,
+                              const float* s1, float* cs, const char* yb,
+                              const int* conf)
+{
+    int tid = threadIdx.x;
+    // pairwise AUC (binary only): wins over (pos, neg) pairs, ties 0.5 —
+    // the Mann-Whitney statistic (== average-rank AUC). Every partial sum
+    // is a multiple of 0.5 below 2^24, so the fp32 total does not depend
+    // on the summation order.
+    __shared__ float auc_wins;
+    __shared__ int npos_s, nneg_s;
+    if (tid == 0) { auc_wins = 0.f; npos_s = 0; nneg_s = 0; }
+    __syncthreads();
+    if (kk == 2) {
+        // compact the scores by label: positives fill cs from the front,
+        // negatives from the back (one LDS atomic per wave and label)
+        int lane = tid & (WAVE - 1);
+        unsigned long long below = (1ull << lane) - 1ull;
+        for (int i0 = 0; i0 < n_e; i0 += blockDim.x) {
+            int i = i0 + tid;
+            bool in = i < n_e;
+            bool ps = in && yb[in ? i : 0];
+            bool ng = in && !ps;
+            float sc = s1[in ? i : 0];
+            unsigned long long mp = __ballot(ps), mn = __ballot(ng);
+            int bp = 0, bn = 0;
+            if (lane == 0) {
+                bp = atomicAdd(&npos_s, __popcll(mp));
+                bn = atomicAdd(&nneg_s, __popcll(mn));
+            }
+            bp = __shfl(bp, 0, WAVE);
+            bn = __shfl(bn, 0, WAVE);
+            if (ps) cs[bp + __popcll(mp & below)] = sc;
+            if (ng) cs[n_e - 1 - (bn + __popcll(mn & below))] = sc;
+        }
+        __syncthreads();
+        int npos = npos_s, nneg = n_e - npos;
+        int total = npos * nneg;  // <= 2^20 for n_e <= 2048
+        const float* pos = cs;
+        const float* neg = cs + npos;
+        float wins = 0.f;
+        if (total > 0) {
+            // pair q = i*nneg + j; a thread walks q = tid, tid + B, ... and
+            // keeps (i, j) by adding (B / nneg, B % nneg) with one carry
+            int B = blockDim.x;
+            int di = B / nneg, dj = B - di * nneg;
+            int i = tid / nneg, j = tid - i * nneg;
+            for (int q0 = tid; q0 < total; q0 += CH * B) {
+                float pv[CH], nv[CH];
+                bool ok[CH];
+#pragma unroll
+                for (int u = 0; u < CH; ++u) {
+                    ok[u] = q0 + u * B < total;
+                    pv[u] = pos[min(i, npos - 1)];
+                    nv[u] = neg[j];
+                    i += di; j += dj;
+                    if (j >= nneg) { j -= nneg; i += 1; }
+                }
+#pragma unroll
+                for (int u = 0; u < CH; ++u) {
+                    float w = pv[u] > nv[u] ? 1.f
+                                            : (pv[u] == nv[u] ? 0.5f : 0.f);
+                    wins += ok[u] ? w : 0.f;
+                }
+            }
+        }
+        // block reduce via wave shuffles: 256 serialized LDS atomics were
+        // ~1/3 of this kernel's time
+        wins = wave_sum(wins);
+        if (lane == 0) atomicAdd(&auc_wins, wins);
+    }
+    __syncthreads();
+
+    if (tid == 0) {
+        int n = n_e;
+        int correct = 0;
+        float prec = 0.f, rec = 0.f, f1 = 0.f;
+        for (int c = 0; c < kk; ++c) {
+            int tp = conf[c * kk + c];
+            correct += tp;
+            int pred_tot = 0, true_tot = 0;
+            for (int t2 = 0; t2 < kk; ++t2) {
+                pred_tot += conf[t2 * kk + c];
+                true_tot += conf[c * kk + t2];
+            }
+            float p = pred_tot > 0 ? (float)tp / pred_tot : 0.f;
+            float q = true_tot > 0 ? (float)tp / true_tot : 0.f;
+            prec += p;
+            rec += q;
+            f1 += (p + q) > 0.f ? 2.f * p * q / (p + q) : 0.f;
+        }
+        float* o = out_row;
+        o[0] = (float)correct / n;
+        o[1] = prec / kk;
+        o[2] = rec / kk;
+        o[3] = f1 / kk;
+        if (kk == 2) {
+            int npos = npos_s, nneg = n - npos_s;
+            o[4] = (npos == 0 || nneg == 0)
+                       ? 0.5f
+                       : auc_wins / ((float)npos * nneg);
+        } else {
+            o[4] = -1.f;  // AUC undefined for k > 2 (reference parity)
+        }
+    }
+}
+
 __global__ void __launch_bounds__(256)
 eval_metrics_kernel(EvalArgs a)
 {
@@ -2200,106 +2319,84 @@ eval_metrics_kernel(EvalArgs a)
         __syncthreads();
     }
 
-    // pairwise AUC (binary only): wins over (pos, neg) pairs, ties 0.5 —
-    // the Mann-Whitney statistic (== average-rank AUC). Every partial sum
-    // is a multiple of 0.5 below 2^24, so the fp32 total does not depend
-    // on the summation order.
-    __shared__ float auc_wins;
-    __shared__ int npos_s, nneg_s;
-    if (tid == 0) { auc_wins = 0.f; npos_s = 0; nneg_s = 0; }
-    __syncthreads();
-    if (kk == 2) {
-        // compact the scores by label: positives fill cs from the front,
-        // negatives from the back (one LDS atomic per wave and label)
-        int lane = tid & (WAVE - 1);
-        unsigned long long below = (1ull << lane) - 1ull;
-        for (int i0 = 0; i0 < n_e; i0 += blockDim.x) {
-            int i = i0 + tid;
-            bool in = i < n_e;
-            bool ps = in && yb[in ? i : 0];
-            bool ng = in && !ps;
-            float sc = s1[in ? i : 0];
-            unsigned long long mp = __ballot(ps), mn = __ballot(ng);
-            int bp = 0, bn = 0;
-            if (lane == 0) {
-                bp = atomicAdd(&npos_s, __popcll(mp));
-                bn = atomicAdd(&nneg_s, __popcll(mn));
-            }
-            bp = __shfl(bp, 0, WAVE);
-            bn = __shfl(bn, 0, WAVE);
-            if (ps) cs[bp + __popcll(mp & below)] = sc;
-            if (ng) cs[n_e - 1 - (bn + __popcll(mn & below))] = sc;
-        }
-        __syncthreads();
-        int npos = npos_s, nneg = n_e - npos;
-        int total = npos * nneg;  // <= 2^20 for n_e <= 2048
-        const float* pos = cs;
-        const float* neg = cs + npos;
-        float wins = 0.f;
-        if (total > 0) {
-            // pair q = i*nneg + j; a thread walks q = tid, tid + B, ... and
-            // keeps (i, j) by adding (B / nneg, B % nneg) with one carry
-            int B = blockDim.x;
-            int di = B / nneg, dj = B - di * nneg;
-            int i = tid / nneg, j = tid - i * nneg;
-            for (int q0 = tid; q0 < total; q0 += CH * B) {
-                float pv[CH], nv[CH];
-                bool ok[CH];
-#pragma unroll
-                for (int u = 0; u < CH; ++u) {
-                    ok[u] = q0 + u * B < total;
-                    pv[u] = pos[min(i, npos - 1)];
-                    nv[u] = neg[j];
-                    i += di; j += dj;
-                    if (j >= nneg) { j -= nneg; i += 1; }
-                }
-#pragma unroll
-                for (int u = 0; u < CH; ++u) {
-                    float w = pv[u] > nv[u] ? 1.f
-                                            : (pv[u] == nv[u] ? 0.5f : 0.f);
-                    wins += ok[u] ? w : 0.f;
-                }
-            }
-        }
-        // block reduce via wave shuffles: 256 serialized LDS atomics were
-        // ~1/3 of this kernel's time
-        wins = wave_sum(wins);
-        if (lane == 0) atomicAdd(&auc_wins, wins);
-    }
-    __syncthreads();
+    eval_epilogue(a.out + (long)r * 5, n_e, kk, s1, cs, yb, conf);
+}
 
-    if (tid == 0) {
-        int n = n_e;
-        int correct = 0;
-        float prec = 0.f, rec = 0.f, f1 = 0.f;
-        for (int c = 0; c < kk; ++c) {
-            int tp = conf[c * kk + c];
-            correct += tp;
-            int pred_tot = 0, true_tot = 0;
-            for (int t2 = 0; t2 < kk; ++t2) {
-                pred_tot += conf[t2 * kk + c];
-                true_tot += conf[c * kk + t2];
-            }
-            float p = pred_tot > 0 ? (float)tp / pred_tot : 0.f;
-            float q = true_tot > 0 ? (float)tp / true_tot : 0.f;
-            prec += p;
-            rec += q;
-            f1 += (p + q) > 0.f ? 2.f * p * q / (p + q) : 0.f;
-        }
-        float* o = a.out + (long)r * 5;
-        o[0] = (float)correct / n;
-        o[1] = prec / kk;
-        o[2] = rec / kk;
-        o[3] = f1 / kk;
-        if (kk == 2) {
-            int npos = npos_s, nneg = n - npos_s;
-            o[4] = (npos == 0 || nneg == 0)
-                       ? 0.5f
-                       : auc_wins / ((float)npos * nneg);
-        } else {
-            o[4] = -1.f;  // AUC undefined for k > 2 (reference parity)
+// K13 for the MLP family: block r runs node nodes[r]'s forward on MFMA
+// (mlp_forward, the chain tick_pens_mlp_kernel scores candidates with) over
+// its evaluation rows, in chunks of `tile` rows staged in LDS, and ends in
+// the same metrics epilogue. Two addressing modes, as EvalArgs: per-node
+// shards (eval_counts set: X/Y are [n_local, n_eval(, d_in)] arenas indexed
+// by the LOCAL ROW ID nodes[r], eval_counts[node] rows of them live) or one
+// shared set (X is [n_eval, d_in]). Of MlpArgs only params, nodes, X, Y,
+// layout, n_layers, D and d_in are read.
+struct EvalMlpArgs {
+    MlpArgs m;
+    float* out;              // [R, 5] acc, prec, rec, f1, auc
+    const int* eval_counts;  // [n_local], or null: shared set
+    int n_eval;              // rows of the shared set / row stride of a shard
+    int tile;                // rows forwarded per chunk (eval_mlp_tile)
+};
+
+__global__ void __launch_bounds__(256)
+eval_mlp_kernel(EvalMlpArgs p)
+{
+    const MlpArgs& a = p.m;
+    int r = blockIdx.x;
+    int node = a.nodes[r];
+    int tid = threadIdx.x;
+    int n_e = p.n_eval;
+    const float* Xb = a.X;
+    const float* Yb = a.Y;
+    if (p.eval_counts) {
+        Xb = a.X + (long)node * p.n_eval * a.d_in;
+        Yb = a.Y + (long)node * p.n_eval;
+        n_e = min(p.eval_counts[node], p.n_eval);
+        if (n_e <= 0) {
+            if (tid == 0)
+                for (int e = 0; e < 5; ++e) p.out[(long)r * 5 + e] = -2.f;
+            return;
         }
     }
+    extern __shared__ float sm[];
+    float* W = sm;                       // D
+    float* s1 = W + a.D;                 // n_e: positive-class score
+    float* cs = s1 + n_e;                // n_e: s1 compacted by label
+    char* yb = (char*)(cs + n_e);        // n_e: binarized label
+    int* conf = (int*)(yb + ((n_e + 15) & ~15));  // k*k confusion
+    // forward scratch: tile x (d_in + act_total)
+    float* act = (float*)(conf + EVAL_KMAX * EVAL_KMAX);
+    int k = a.layout[4 * (a.n_layers - 1) + 3];
+
+    copy_row(W, a.params + (long)node * a.D, a.D);
+    for (int e = tid; e < k * k; e += blockDim.x) conf[e] = 0;
+
+    for (int s0 = 0; s0 < n_e; s0 += p.tile) {
+        int m = min(p.tile, n_e - s0);
+        copy_row<16>(act, Xb + (long)s0 * a.d_in, m * a.d_in);
+        __syncthreads();
+        const float* head = mlp_forward(a, W, act, m);
+        // (thread = sample, block-strided); ascending scan, strict > — the
+        // first maximum wins, as torch.argmax
+        for (int s = tid; s < m; s += blockDim.x) {
+            const float* z = head + s * k;
+            float yv = Yb[s0 + s];
+            float best = z[0];
+            int bj = 0;
+            for (int j = 1; j < k; ++j) {
+                if (z[j] > best) { best = z[j]; bj = j; }
+            }
+            int yt = (int)yv;
+            s1[s0 + s] = k > 1 ? z[1] : z[0];
+            yb[s0 + s] = (char)(yt == 1 ? 1 : 0);
+            // a label outside [0, k) has no confusion row
+            if ((unsigned)yt < (unsigned)k) atomicAdd(&conf[yt * k + bj], 1);
+        }
+        // the head is read out before the next chunk overwrites act
+        __syncthreads();
+    }
+
+    eval_epilogue(p.out + (long)r * 5, n_e, k, s1, cs, yb, conf);
 }
 
 // ---------------------------------------------------------------------------
@@ -3834,6 +3931,103 @@ torch::Tensor eval_metrics_scores(torch::Tensor scores, torch::Tensor Y,
     return out;
 }
 
+// eval_mlp_kernel's LDS next to the forward scratch: model + scores + their
+// label-compacted copy + binarized labels + confusion, and the epilogue's
+// three static words (rounded up to 16 B).
+static size_t eval_mlp_fixed_smem(int64_t D, int64_t n_eval)
+{
+    return sizeof(float) * ((size_t)D + 2 * (size_t)n_eval)
+        + (((size_t)n_eval + 15) & ~(size_t)15) * sizeof(char)
+        + sizeof(int) * EVAL_KMAX * EVAL_KMAX + 16;
+}
+
+// Rows eval_mlp_kernel forwards per chunk: the most that fit the 160 KB LDS
+// budget, at most n_eval and 512. 0 = the shape does not fit: fewer than 16
+// rows of scratch, or n_eval > 2048 (the pairwise AUC is O(n_eval^2) per
+// block and its pair count assumes n_eval <= 2048).
+static int64_t eval_mlp_tile(int64_t D, int64_t d_in, int64_t act_total,
+                             int64_t n_eval)
+{
+    if (D < 1 || d_in < 1 || act_total < 1 || n_eval < 1 || n_eval > 2048)
+        return 0;
+    int64_t left = 160 * 1024 - (int64_t)eval_mlp_fixed_smem(D, n_eval);
+    int64_t room = left / (int64_t)(sizeof(float) * (d_in + act_total));
+    if (left <= 0 || room < 16) return 0;
+    return std::min<int64_t>({room, n_eval, 512});
+}
+
+torch::Tensor eval_mlp(torch::Tensor params, torch::Tensor nodes,
+                       torch::Tensor X, torch::Tensor Y, torch::Tensor layout,
+                       int64_t n_layers, torch::Tensor eval_counts)
+{
+    CHECK_DEV(params); CHECK_DEV(nodes); CHECK_DEV(X); CHECK_DEV(Y);
+    CHECK_DEV(layout);
+    TORCH_CHECK(params.scalar_type() == torch::kFloat32 &&
+                    X.scalar_type() == torch::kFloat32 &&
+                    Y.scalar_type() == torch::kFloat32,
+                "params, X and Y must be float32");
+    TORCH_CHECK(nodes.scalar_type() == torch::kInt32 &&
+                    layout.scalar_type() == torch::kInt32,
+                "nodes and layout must be int32");
+    TORCH_CHECK(params.dim() == 2, "params must be [n_local, D]");
+    TORCH_CHECK(n_layers >= 1 && layout.numel() == 4 * n_layers,
+                "mlp layout must hold n_layers x (w_off, b_off, in, out)");
+    bool per_node = eval_counts.defined() && eval_counts.numel();
+    int64_t D = params.size(1);
+    auto lay = layout.cpu();
+    const int* Lh = lay.data_ptr<int>();
+    int64_t d_in = Lh[2], act_total = 0;
+    for (int l = 0; l < n_layers; ++l) {
+        int64_t w_off = Lh[4 * l], b_off = Lh[4 * l + 1];
+        int64_t fin = Lh[4 * l + 2], fout = Lh[4 * l + 3];
+        TORCH_CHECK(fin >= 1 && fout >= 1 && w_off >= 0 && b_off >= 0 &&
+                        w_off + fin * fout <= D && b_off + fout <= D &&
+                        fin == (l ? Lh[4 * l - 1] : d_in),
+                    "mlp layout does not fit a params row of ", D);
+        act_total += fout;
+    }
+    int64_t k = Lh[4 * (n_layers - 1) + 3];
+    TORCH_CHECK(k <= EVAL_KMAX, "n_classes > ", EVAL_KMAX, " unsupported");
+    int64_t n_eval;
+    if (per_node) {
+        CHECK_DEV(eval_counts);
+        TORCH_CHECK(eval_counts.scalar_type() == torch::kInt32,
+                    "eval_counts must be int32");
+        TORCH_CHECK(X.dim() == 3 && X.size(2) == d_in && Y.dim() == 2 &&
+                        Y.size(0) == X.size(0) && Y.size(1) == X.size(1) &&
+                        eval_counts.numel() == X.size(0),
+                    "per-node mode: X [n_local, S, d_in], Y [n_local, S],"
+                    " eval_counts [n_local]");
+        n_eval = X.size(1);
+    } else {
+        TORCH_CHECK(X.dim() == 2 && X.size(1) == d_in &&
+                        Y.numel() == X.size(0),
+                    "shared-set mode: X [n, d_in], Y [n]");
+        n_eval = X.size(0);
+    }
+    int R = nodes.size(0);
+    auto out = torch::empty({R, 5}, params.options());
+    if (R == 0) return out;
+    int64_t tile = eval_mlp_tile(D, d_in, act_total, n_eval);
+    TORCH_CHECK(tile > 0, "eval_mlp: shape does not fit (D=", D, ", d_in=",
+                d_in, ", act_total=", act_total, ", n_eval=", n_eval, ")");
+    EvalMlpArgs p{};
+    p.m.params = params.data_ptr<float>();
+    p.m.nodes = nodes.data_ptr<int>();
+    p.m.X = X.data_ptr<float>();
+    p.m.Y = Y.data_ptr<float>();
+    p.m.layout = layout.data_ptr<int>();
+    p.m.n_layers = n_layers; p.m.D = D; p.m.d_in = d_in;
+    p.out = out.data_ptr<float>();
+    p.eval_counts = per_node ? eval_counts.data_ptr<int>() : nullptr;
+    p.n_eval = n_eval; p.tile = tile;
+    // the +16 of the fixed part stands for the epilogue's static words
+    size_t smem = eval_mlp_fixed_smem(D, n_eval) - 16 +
+                  sizeof(float) * (size_t)tile * (d_in + act_total);
+    launch_kernel(eval_mlp_kernel, R, 256, smem, current_stream(), p);
+    return out;
+}
+
 // ---------------------------------------------------------------------------
 // RoundDriver: one native call per round. It takes the round from the
 // scheduler's RoundSource (csrc/round_source.h), writes the upload layout
@@ -4503,6 +4697,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           "fused per-node eval metrics on a shared eval set (K13)");
     m.def("eval_metrics_scores", &eval_metrics_scores,
           "K13 metrics epilogue on precomputed scores (MLP/torchmod)");
+    // most classes the evaluation kernels take (eval_metrics*, eval_mlp)
+    m.attr("EVAL_KMAX") = EVAL_KMAX;
+    m.def("eval_mlp", &eval_mlp,
+          "K13 for the MLP family: MFMA forward + metrics in one launch, on"
+          " per-node shards or (empty eval_counts) one shared set");
+    m.def("eval_mlp_tile", &eval_mlp_tile,
+          "rows eval_mlp forwards per chunk for (D, d_in, act_total, n_eval);"
+          " 0 when the shape does not fit");
     m.def("tick_kmeans", &tick_kmeans,
           "fused centroid merge + assign/EMA k-means tick (K11)");
 }
