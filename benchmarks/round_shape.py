@@ -17,7 +17,9 @@ check that every round has the expected number. It then fits
 duration = a + b * (largest deliveries per row) by least squares and reports
 the thin launches, the per-round totals and how often a round's evaluation
 kernel ends after the next round's first tick launch begins. ``--timed-from
-W`` leaves the warm-up rounds out of those figures."""
+W`` leaves the warm-up rounds out of those figures. ``--pack-levels CAP``
+replays with the level packer at that row cap (0: the default packer); give
+the value the traced run used."""
 import argparse
 import csv
 import os
@@ -71,12 +73,20 @@ def round_launches(flat):
     return out
 
 
-def replay(r1):
+def replay(r1, pack_levels=None):
+    """The launches of rounds 0..r1. ``pack_levels``: the level packer's row
+    cap (0: off); None takes what the runner's ``start()`` would set."""
     sim = bench_simulator()
+    if pack_levels is None:
+        pack_levels = sim._pack_levels_cap()
+    sim.scheduler.set_pack_levels(pack_levels)
     rounds = []
     for r in range(r1 + 1):
         sim.scheduler.next_round_flat(r)
         rounds.append(round_launches(sim._maybe_merge(sim.scheduler.last_flat)))
+    packed, refused = sim.scheduler.pack_level_stats()
+    print(f"level packer: row cap {pack_levels}, packed {packed} rounds, "
+          f"left {refused} to the default packer")
     return rounds
 
 
@@ -184,10 +194,14 @@ def main():
                     help="kernel-trace CSV of the bench line to join")
     ap.add_argument("--timed-from", type=int, default=0,
                     help="first round that counts in the fit (bench warm-up)")
+    ap.add_argument("--pack-levels", type=int, default=None,
+                    help="row cap of the level packer, 0 for the default "
+                         "packer (default: what the runner sets, which "
+                         "GOSSIPY_PACK_LEVELS overrides)")
     ap.add_argument("--quiet", action="store_true",
                     help="no line per launch, sums only")
     args = ap.parse_args()
-    rounds = replay(args.r1)
+    rounds = replay(args.r1, args.pack_levels)
     tot = []
     for r in range(args.r0, args.r1 + 1):
         for kind, rows, mx, n in rounds[r]:

@@ -167,6 +167,25 @@ which order, is the extension's `ROUND_ARRAY_NAMES` (14 names) and
 device tensor, whose `lens` has another count, a negative entry or a sum past
 the buffer, or whose tick pointers are empty or differ in length raises
 `RuntimeError` and launches nothing.
+
+## Launch order within a round
+
+The native scheduler hands a round over as launch groups. Its default packer
+merges ticks greedily, so a launch lasts as long as its longest receiver row.
+`NativeSchedulerAdapter.set_pack_levels(cap)` orders the rounds generated
+after the call by dependency level instead (`csrc/round_levels.h`): a
+delivery runs in the first launch after the previous delivery to its
+receiver and after the delivery that produced the state its slot holds, at
+most `cap` deliveries per row, so the launches of a round add up to its
+critical path. Every delivery computes what it computed before; results are
+bit-equal. Rounds with pull or reply events (PULL, PUSH_PULL) keep the
+default packer; `pack_level_stats()` counts both kinds. `start()` turns it
+on, with `cap = 1`, on the single-rank HIP fast path for logreg (plain,
+partitioned, limited merge) and pegasos/adaline, and leaves it off for the
+other families; `GOSSIPY_PACK_LEVELS=0` turns it off and
+`GOSSIPY_PACK_LEVELS=<cap>` sets the cap for every family of that path.
+Multi-rank runs, the tokenized, PENS and all2all simulators and the torchmod
+group replay never use it. Measurements: `profiles/level_packing.md`.
 """
 
 

@@ -21,6 +21,7 @@
 #include <pybind11/stl.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdint>
 #include <map>
@@ -34,6 +35,7 @@
 #include <vector>
 
 #include "round_layout.h"
+#include "round_levels.h"
 #include "round_prefetch.h"
 #include "round_source.h"
 
@@ -208,16 +210,9 @@ static std::vector<int32_t> compute_merge_bounds(
 // chains no longer fragment the round. Returns packed arrays in the
 // executors' format.
 // ---------------------------------------------------------------------------
-// the packed arrays, in plain C++ (no Python objects: a worker thread may
-// compute them without the GIL); emit_packed turns them into the dict
-struct PackedRound {
-    std::vector<int32_t> snap_nodes, snap_slots, snap_tptr{0};
-    std::vector<int32_t> recv_nodes, recv_nptr{0}, recv_tptr{0};
-    std::vector<int32_t> del_slots, reply_slots, del_pids, del_owners;
-    std::vector<int32_t> rep_nodes, rep_nptr{0}, rep_tptr{0};
-    std::vector<int32_t> rep_slots, rep_reply_slots, rep_pids, rep_owners;
-    std::vector<int32_t> pull_tptr{};
-};
+// the packed arrays are a PackedRound (round_levels.h), in plain C++ (no
+// Python objects: a worker thread may compute them without the GIL);
+// emit_packed turns them into the dict
 
 static PackedRound pack_round_compute(
     const std::vector<int32_t>& snap_nodes, const std::vector<int32_t>& snap_slots,
@@ -563,6 +558,9 @@ struct RoundData {
     std::vector<int32_t> rep_nodes, rep_tptr{0}, rep_nptr{0};
     std::vector<int32_t> rep_slots, rep_owners, rep_pids;
     PackedRound packed;
+    // the level packer's row cap for this round (0: pack_round_compute),
+    // fixed when the round is generated
+    int pack_levels = 0;
     int64_t sent = 0, failed = 0, total_size = 0, n_slots = 0;
     std::vector<int64_t> eval_nodes;  // empty: no evaluation this round
 };
@@ -653,9 +651,9 @@ public:
             RoundPrefetch<RoundData>* gen = gen_.get();
             const int64_t n = n_;
             prefetch_ = std::make_unique<RoundPrefetch<RoundData>>(
-                [gen, n](int64_t r) {
+                [this, gen, n](int64_t r) {
                     RoundData d = gen->take(r);
-                    pack_generated(d, n);
+                    pack_generated(d, n, &levels_);
                     return d;
                 },
                 next_r_);
@@ -667,7 +665,8 @@ public:
                 // which keeps producing until it is stopped in turn)
                 rest = prefetch_->drain();
                 unpacked = gen_->drain();
-                for (auto& d : unpacked) pack_generated(d, n_);
+                // both workers have stopped: levels_ is this thread's now
+                for (auto& d : unpacked) pack_generated(d, n_, &levels_);
             }
             prefetch_.reset();
             gen_.reset();
@@ -681,7 +680,16 @@ protected:
     // + pack_generated (launch packing: none of it)
     RoundData compute_round(int64_t r);
     RoundData generate_round(int64_t r);
-    static void pack_generated(RoundData& rd, int64_t n_nodes);
+    // the level packer's state, for whichever thread packs: the packing
+    // worker while there is one, else the caller
+    struct LevelState {
+        LevelPacker packer;
+        std::atomic<int64_t> packed{0}, fallbacks{0};
+    };
+    static void pack_generated(RoundData& rd, int64_t n_nodes,
+                               LevelState* lv);
+    LevelState levels_;
+    std::atomic<int> pack_levels_{0};
     py::dict emit_round(RoundData& d);
     // the next round from wherever it is waiting: rounds handed back or
     // left by a stopped worker first, then the worker, else computed now.
@@ -740,6 +748,23 @@ public:
     // arrays and the multi-rank merge bounds are skipped — at 50k nodes
     // that halves the emit phase
     void set_lean(bool v) { lean_ = v; }
+    // Pack rounds by dependency level (round_levels.h) with at most `cap`
+    // deliveries per receiver row; 0, the default, keeps pack_round_compute
+    // for every round. The generator stamps the value into each round it
+    // produces, so rounds already generated ahead keep the packing they
+    // were generated for, and the packing worker never reads a value that
+    // changes under it. A round the level packer refuses goes to
+    // pack_round_compute and counts as a fallback.
+    void set_pack_levels(int cap)
+    {
+        if (cap < 0) throw std::invalid_argument("set_pack_levels: cap < 0");
+        pack_levels_.store(cap);
+    }
+    // (rounds the level packer packed, rounds it left to pack_round_compute)
+    py::tuple pack_level_stats() const
+    {
+        return py::make_tuple(levels_.packed.load(), levels_.fallbacks.load());
+    }
 protected:
     bool lean_ = false;
     struct DEv { int32_t v0, v1, v2, v3, next; };
@@ -1049,6 +1074,7 @@ RoundData NativeScheduler::generate_round(int64_t r)
 {
     const int64_t t0 = r * delta_, t1 = (r + 1) * delta_;
     RoundData rd;
+    rd.pack_levels = pack_levels_.load();
     int64_t &sent = rd.sent, &failed = rd.failed, &total_size = rd.total_size;
     auto &snap_nodes = rd.snap_nodes, &snap_slots = rd.snap_slots,
          &snap_tptr = rd.snap_tptr;
@@ -1286,8 +1312,21 @@ RoundData NativeScheduler::generate_round(int64_t r)
 // The second half of a round: a pure function of the generated events (it
 // touches no scheduler state), so a second worker may run it while the
 // first already generates the next round.
-void NativeScheduler::pack_generated(RoundData& rd, int64_t n_nodes)
+void NativeScheduler::pack_generated(RoundData& rd, int64_t n_nodes,
+                                     LevelState* lv)
 {
+    if (rd.pack_levels > 0) {
+        const char* why = lv->packer.pack(
+            rd.snap_nodes, rd.snap_slots, rd.snap_tptr, rd.recv_nodes,
+            rd.recv_nptr, rd.recv_tptr, rd.del_slots, rd.reply_slots,
+            rd.del_pids, rd.pull_nodes, rd.rep_nodes, rd.del_owners, n_nodes,
+            rd.n_slots, rd.pack_levels, &rd.packed);
+        if (!why) {
+            ++lv->packed;
+            return;
+        }
+        ++lv->fallbacks;
+    }
     rd.packed = pack_round_compute(
         rd.snap_nodes, rd.snap_slots, rd.snap_tptr, rd.recv_nodes,
         rd.recv_nptr, rd.recv_tptr, rd.del_slots, rd.reply_slots,
@@ -1299,7 +1338,7 @@ void NativeScheduler::pack_generated(RoundData& rd, int64_t n_nodes)
 RoundData NativeScheduler::compute_round(int64_t r)
 {
     RoundData rd = generate_round(r);
-    pack_generated(rd, n_);
+    pack_generated(rd, n_, &levels_);
     return rd;
 }
 
@@ -1848,6 +1887,8 @@ PYBIND11_MODULE(_gossip_sched, m)
         // every user of it (the runner holds both)
         .def("round_source", &NativeScheduler::round_source)
         .def("set_lean", &NativeScheduler::set_lean)
+        .def("set_pack_levels", &NativeScheduler::set_pack_levels)
+        .def("pack_level_stats", &NativeScheduler::pack_level_stats)
         .def("set_prefetch", &NativeScheduler::set_prefetch);
     py::class_<NativeTokenizedScheduler>(m, "NativeTokenizedScheduler")
         .def(py::init<int64_t, int64_t, int, int64_t, double, double, int,

@@ -887,6 +887,39 @@ class BatchedGossipSimulator(SimulationEventSender):
             and not env.get("GOSSIPY_SB_MAX")
         )
 
+    #: row cap of the level packer where it is on by default
+    PACK_LEVELS_DEFAULT = 1
+
+    def _pack_levels_cap(self) -> int:
+        """Row cap of the scheduler's level packer for this simulator's
+        fast-path rounds; 0 keeps the default packer. ``GOSSIPY_PACK_LEVELS``
+        decides where it is set (``0``: off, ``<cap>``: that cap, for any
+        family of the fast path). Otherwise it is on where it was measured
+        to gain (profiles/level_packing.md), the families whose round is a
+        chain of short launches: logreg and MLP with whole-model merges
+        (logreg with limited merge too) and pegasos/adaline. The
+        partitioned and sampled variants, limited-merge MLP and matrix
+        factorization were not measured and keep the default packer."""
+        v = os.environ.get("GOSSIPY_PACK_LEVELS")
+        if v is not None and v != "":
+            return max(int(v), 0)
+        spec = self.spec
+        whole = (
+            getattr(spec, "n_parts", 0) == 0
+            and getattr(spec, "sample_size", 0) == 0
+        )
+        if spec.family in ("pegasos", "adaline"):
+            return self.PACK_LEVELS_DEFAULT
+        if spec.family == "logreg" and whole:
+            return self.PACK_LEVELS_DEFAULT
+        if (
+            spec.family == "mlp"
+            and whole
+            and getattr(spec, "age_diff_threshold", None) is None
+        ):
+            return self.PACK_LEVELS_DEFAULT
+        return 0
+
     def _maybe_merge(
         self, f: dict, pack: bool = True, force_py_pack: bool = False
     ) -> dict:
@@ -1288,6 +1321,8 @@ class BatchedGossipSimulator(SimulationEventSender):
             # Any knob that routes around the packed path needs the full
             # arrays, so lean stays off there.
             self.scheduler.set_lean(True)
+            if hasattr(self.scheduler, "set_pack_levels"):
+                self.scheduler.set_pack_levels(self._pack_levels_cap())
             # schedule generation moves to the scheduler's C++ worker
             # thread; the next_round_flat(r + 1) below then returns as soon
             # as the round is converted (GOSSIPY_NO_SCHED_THREAD=1: A/B)

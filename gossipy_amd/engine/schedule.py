@@ -1689,6 +1689,24 @@ def _adapter_set_prefetch(self, v: bool) -> None:
 NativeSchedulerAdapter.set_prefetch = _adapter_set_prefetch
 
 
+def _adapter_set_pack_levels(self, cap: int) -> None:
+    """Pack the rounds generated from now on by dependency level, at most
+    ``cap`` deliveries per receiver row (csrc/round_levels.h); 0 is the
+    default packer. Rounds with pull or reply events keep the default packer
+    whatever the value (see :meth:`pack_level_stats`)."""
+    self._native.set_pack_levels(int(cap))
+
+
+def _adapter_pack_level_stats(self):
+    """``(rounds the level packer packed, rounds it refused)`` so far; a
+    refused round went through the default packer."""
+    return tuple(self._native.pack_level_stats())
+
+
+NativeSchedulerAdapter.set_pack_levels = _adapter_set_pack_levels
+NativeSchedulerAdapter.pack_level_stats = _adapter_pack_level_stats
+
+
 def _adapter_round_source(self):
     """Capsule over the native scheduler's ``RoundSource`` (csrc/
     round_source.h): what the extension's ``RoundDriver`` takes its rounds
