@@ -1801,6 +1801,22 @@ class HIPBackend(TorchBackend):
             self._part_cache[key] = hit
         return hit
 
+    def mlp_tick_path(self, spec, data) -> str:
+        """Which kernel the plain MLP tick of ``spec`` runs on the shards of
+        ``data``: ``"lds"`` (``tick_mlp_kernel``: model row, staged minibatch
+        and activations in one workgroup's 160 KB of LDS) whenever that
+        fits, else ``"wide"`` (``tick_mlp_wide_kernel``: rows in device
+        memory, the minibatch read from the arena). ``GOSSIPY_MLP_WIDE=1``
+        forces ``"wide"``; with ``=0`` a shape past the budget raises the
+        budget error instead. Partitioned, sampled and PENS MLP ticks have
+        the LDS kernels only."""
+        if spec.family != "mlp" or spec.n_parts > 0 or spec.sample_size > 0:
+            raise ValueError("mlp_tick_path: a plain MLPSpec is required")
+        return self.ext.mlp_tick_path(
+            list(spec.dims), spec.batch_size, data.x.shape[1],
+            _MODE_ID[spec.mode],
+        )
+
     def _family_call(self, spec, dev):
         """The one mapping from a spec to extension arguments. Returns
         ``(name, args, chan)``:

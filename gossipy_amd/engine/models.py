@@ -238,6 +238,18 @@ class MLPSpec(_PartitionMixin):
     :class:`LogRegSpec`; the two are mutually exclusive, and neither
     combines with ``pass_through`` (PASS is an error for both handlers,
     gossipy/model/handler.py:449-452, 491-494).
+
+    On the GPU the plain tick (every mode, ``pass_through``, limited merge)
+    takes any shape. While ``4 * (w * D + rows * (d_in + sum(out)) +
+    2 * rows * max(width))`` bytes fit one workgroup's 160 KB of LDS
+    (``w = 2`` for UPDATE_MERGE, else 1; ``rows`` the largest minibatch) it
+    runs the LDS-resident kernel; past that, e.g. 784-100-10, the
+    global-resident wide kernel, which returns the same bits on a shape both
+    take. ``HIPBackend.mlp_tick_path`` tells which, and
+    ``GOSSIPY_MLP_WIDE=1`` / ``=0`` force / forbid the wide one. Still bound
+    to the LDS budget: ``n_parts``, ``sample_size`` and the PENS event, which
+    raise a budget error past it, and the one-launch per-node evaluation,
+    which falls back to the per-node loop.
     """
 
     d_in: int

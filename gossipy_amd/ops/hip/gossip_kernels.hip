@@ -22,6 +22,9 @@
 //                           one wave per node, weights in registers.
 //   tick_mlp_kernel       — K3/K4 generalized: fused MLP fwd/bwd/SGD
 //                           (gossipy/model/nn.py:91-99).
+//   tick_mlp_wide_kernel  — the same tick for models past the LDS budget
+//                           (784-100-10 and up): model rows in device
+//                           memory, the minibatch read from the arena.
 //   tick_mlp_comp_kernel  — the MLP tick under partitioned / sampled
 //                           gossip (gossipy/model/handler.py:426-525),
 //                           same SGD body, templated on the merge policy.
@@ -69,6 +72,7 @@
 #include <atomic>
 #include <chrono>
 #include <deque>
+#include <map>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -1547,6 +1551,9 @@ struct MlpArgs {
     int n_layers, Smax, D, act_max, d_in;
     float lr, wd;
     int epochs, bs, mode, update_only;
+    // tick_mlp_wide_kernel only: the device workspace and its per-block row
+    // stride in floats (0 = no workspace, ws is then null)
+    float* ws; long ws_row;
     int lim;  // limited-merge threshold L (LIM kernel only); last member
 };
 
@@ -1614,14 +1621,10 @@ DEV_INLINE f32x4_t mfma_kloop(int Kdim, LoadA la, LoadB lb)
     return acc;
 }
 
-// Forward pass H = X · Wᵀ + b of every layer over the m rows staged at act
-// (ReLU between layers, raw head), on MFMA. The activations are laid out
-// layer after layer behind the input: act[l] is [m, out_l]. Returns the
-// head's [m, k] activations. The caller's barrier must stand between the
-// staging of the input (and of W) and this call; a barrier follows each
-// layer.
-DEV_INLINE float* mlp_forward(const MlpArgs& a, const float* W, float* act,
-                              int m)
+// One layer of the forward pass on MFMA: nxt[m, out_l] = cur[m, in_l] · W_lᵀ
+// + b_l, ReLU unless l is the head. A barrier follows.
+DEV_INLINE void mlp_forward_layer(const MlpArgs& a, const float* W,
+                                  const float* cur, float* nxt, int m, int l)
 {
     const int tid = threadIdx.x;
     const int wave = tid >> 6;
@@ -1629,39 +1632,62 @@ DEV_INLINE float* mlp_forward(const MlpArgs& a, const float* W, float* act,
     const int fr = lane & 15;       // A-row / B-col fragment index
     const int fk = lane >> 4;       // K fragment index (0..3)
     const int nwaves = blockDim.x >> 6;
-    float* cur = act;
-    float* nxt = act + m * a.d_in;
-    for (int l = 0; l < a.n_layers; ++l) {
-        int w_off = a.layout[4 * l], b_off = a.layout[4 * l + 1];
-        int fin = a.layout[4 * l + 2], fout = a.layout[4 * l + 3];
-        int m16 = (m + 15) >> 4, o16 = (fout + 15) >> 4;
-        for (int tile = wave; tile < m16 * o16; tile += nwaves) {
-            int tr = (tile / o16) << 4, tc = (tile % o16) << 4;
-            f32x4_t acc = mfma_kloop(
-                fin,
-                [&](int k0) {
-                    int q = k0 + fk;
-                    return (tr + fr < m && q < fin)
-                               ? cur[(tr + fr) * fin + q] : 0.f;
-                },
-                [&](int k0) {
-                    int q = k0 + fk;
-                    return (tc + fr < fout && q < fin)
-                               ? W[w_off + (tc + fr) * fin + q]
-                               : 0.f;
-                });
-            for (int r = 0; r < 4; ++r) {
-                int row = tr + (fk << 2) + r, col = tc + fr;
-                if (row < m && col < fout) {
-                    float v = acc[r] + W[b_off + col];
-                    if (l < a.n_layers - 1) v = fmaxf(v, 0.f);  // ReLU
-                    nxt[row * fout + col] = v;
-                }
+    int w_off = a.layout[4 * l], b_off = a.layout[4 * l + 1];
+    int fin = a.layout[4 * l + 2], fout = a.layout[4 * l + 3];
+    int m16 = (m + 15) >> 4, o16 = (fout + 15) >> 4;
+    for (int tile = wave; tile < m16 * o16; tile += nwaves) {
+        int tr = (tile / o16) << 4, tc = (tile % o16) << 4;
+        f32x4_t acc = mfma_kloop(
+            fin,
+            [&](int k0) {
+                int q = k0 + fk;
+                return (tr + fr < m && q < fin)
+                           ? cur[(tr + fr) * fin + q] : 0.f;
+            },
+            [&](int k0) {
+                int q = k0 + fk;
+                return (tc + fr < fout && q < fin)
+                           ? W[w_off + (tc + fr) * fin + q]
+                           : 0.f;
+            });
+        for (int r = 0; r < 4; ++r) {
+            int row = tr + (fk << 2) + r, col = tc + fr;
+            if (row < m && col < fout) {
+                float v = acc[r] + W[b_off + col];
+                if (l < a.n_layers - 1) v = fmaxf(v, 0.f);  // ReLU
+                nxt[row * fout + col] = v;
             }
         }
-        __syncthreads();
+    }
+    __syncthreads();
+}
+
+// Forward pass H = X · Wᵀ + b of every layer over the m rows staged at act
+// (ReLU between layers, raw head), on MFMA. The activations are laid out
+// layer after layer behind the input: act[l] is [m, out_l]. Returns the
+// head's [m, k] activations. The caller's barrier must stand between the
+// staging of the input (and of W) and this call; a barrier follows each
+// layer.
+// WIDE (tick_mlp_wide_kernel): the input is not staged, layer 0 reads the m
+// rows at xin in the data arena and act holds the layers' outputs alone.
+// Layer 0 is a call of its own so that each call sees one address space.
+template <bool WIDE = false>
+DEV_INLINE const float* mlp_forward(const MlpArgs& a, const float* W,
+                                    float* act, int m,
+                                    const float* xin = nullptr)
+{
+    const float* cur = act;
+    float* nxt = act + m * a.d_in;
+    int l = 0;
+    if constexpr (WIDE) {
+        mlp_forward_layer(a, W, xin, act, m, 0);
+        nxt = act + m * a.layout[3];
+        l = 1;
+    }
+    for (; l < a.n_layers; ++l) {
+        mlp_forward_layer(a, W, cur, nxt, m, l);
         cur = nxt;
-        nxt = nxt + m * fout;
+        nxt = nxt + m * a.layout[4 * l + 3];
     }
     return cur;
 }
@@ -1672,7 +1698,12 @@ DEV_INLINE float* mlp_forward(const MlpArgs& a, const float* W, float* act,
 // is divided by the age of its partition (apart: arena offset -> partition
 // id) before weight decay. The plain instantiation ignores agev/apart/P and
 // compiles to the scalar-age code unchanged.
-template <bool PART>
+// WIDE (tick_mlp_wide_kernel): W is a row in device memory, the minibatch
+// is read in place from the data arena instead of being staged, act holds
+// the layers' outputs alone and a.act_max is the widest of them. Every
+// operand address, every K-loop and every epilogue expression is the one of
+// the staged form, so the two return the same bits.
+template <bool PART, bool WIDE = false>
 DEV_INLINE void mlp_update(const MlpArgs& a, int node, float* W,
                            float* act, float* grad, int& age,
                            int* agev = nullptr, const int* apart = nullptr,
@@ -1694,9 +1725,12 @@ DEV_INLINE void mlp_update(const MlpArgs& a, int node, float* W,
             int m = min(bsz, c - s0);
             // activations laid out layer after layer: act[l] is [m, out_l];
             // act[-1] (the input) is staged first at act.
-            float* in = act;
-            for (int e = tid; e < m * a.d_in; e += blockDim.x)
-                in[e] = Xn[(long)s0 * a.d_in + e];
+            const float* xin = Xn + (long)s0 * a.d_in;
+            if constexpr (!WIDE) {
+                float* in = act;
+                for (int e = tid; e < m * a.d_in; e += blockDim.x)
+                    in[e] = xin[e];
+            }
             if constexpr (PART) {
                 // self.n_updates += 1 happens before the step
                 // (handler.py:506); first read is the dW epilogue, behind
@@ -1705,7 +1739,7 @@ DEV_INLINE void mlp_update(const MlpArgs& a, int node, float* W,
             }
             __syncthreads();
             // ---- forward: H = X · Wᵀ + b on MFMA
-            float* cur = mlp_forward(a, W, act, m);
+            const float* cur = mlp_forward<WIDE>(a, W, act, m, xin);
             // ---- output grad: softmax-CE on the raw head
             int k = a.layout[4 * (a.n_layers - 1) + 3];
             float* gcur = grad;  // [m, k] for the head, reused per layer
@@ -1732,10 +1766,12 @@ DEV_INLINE void mlp_update(const MlpArgs& a, int node, float* W,
                 int w_off = a.layout[4 * l], b_off = a.layout[4 * l + 1];
                 int fin = a.layout[4 * l + 2], fout = a.layout[4 * l + 3];
                 // activation input of this layer
-                float* ain = act;
-                for (int q = 0; q < l; ++q) ain += m * a.layout[4 * q + 2];
+                const float* ain = act;
+                for (int q = WIDE ? 1 : 0; q < l; ++q)
+                    ain += m * a.layout[4 * q + 2];
                 // (ain now points at act of layer l's input: layers are
-                //  packed input-first, so offset = m*(d_in + hidden_0 + ...))
+                //  packed input-first, so offset = m*(d_in + hidden_0 + ...);
+                //  WIDE: act starts at hidden_0, and layer 0 reads xin)
                 // grad wrt input (needed before W is updated):
                 // dX[m, fin] = G[m, fout] · W[fout, fin], ReLU-masked
                 if (l > 0) {
@@ -1768,8 +1804,10 @@ DEV_INLINE void mlp_update(const MlpArgs& a, int node, float* W,
                     }
                     __syncthreads();
                 }
-                // weight SGD: dW[fout, fin] = Gᵀ[fout, m] · X[m, fin]
-                {
+                // weight SGD: dW[fout, fin] = Gᵀ[fout, m] · X[m, fin], X the
+                // layer's input at bin
+                auto dw_stage = [&](const float* bin)
+                                    __attribute__((always_inline)) {
                     int o16 = (fout + 15) >> 4, q16 = (fin + 15) >> 4;
                     for (int tile = wave; tile < o16 * q16; tile += nwaves) {
                         int tr = (tile / q16) << 4, tc = (tile % q16) << 4;
@@ -1796,7 +1834,7 @@ DEV_INLINE void mlp_update(const MlpArgs& a, int node, float* W,
                             [&](int k0) {
                                 int sidx = k0 + fk;
                                 return (sidx < m && tc + fr < fin)
-                                           ? ain[sidx * fin + tc + fr]
+                                           ? bin[sidx * fin + tc + fr]
                                            : 0.f;
                             });
                         for (int r = 0; r < 4; ++r) {
@@ -1811,7 +1849,10 @@ DEV_INLINE void mlp_update(const MlpArgs& a, int node, float* W,
                             }
                         }
                     }
-                }
+                };
+                // (WIDE: one call per address space, arena rows or LDS)
+                if (WIDE && l == 0) dw_stage(xin);
+                else dw_stage(ain);
                 for (int e = tid; e < fout; e += blockDim.x) {
                     float g = 0.f;
                     for (int s = 0; s < m; ++s) g += gcur[s * fout + e];
@@ -1914,6 +1955,96 @@ tick_mlp_kernel(MlpArgs a)
     __syncthreads();
     for (int e = tid; e < a.D; e += blockDim.x)
         a.params[(long)node * a.D + e] = W[e];
+    if (tid == 0) a.ages[node] = age;
+}
+
+// tick_mlp_kernel for models past the LDS budget: no LDS term scales with D
+// or with batch_rows * d_in. Block per receiver, the same delivery semantics
+// line by line, but
+//   W   is params[node] itself, worked on in place: receivers are unique
+//       within a launch, so only this block touches the row;
+//   W2  (UPDATE_MERGE's trained copy of the received model) is the head of
+//       this block's row of the device workspace a.ws;
+//   X   is read from the data arena by the GEMM stages, never staged;
+//   act / grad hold the layers' outputs and two gradient buffers of the
+//       widest output: in LDS, or (ACT_WS) behind W2 in the workspace row
+//       when a batch's worth of them misses the LDS budget.
+// mlp_update<false, true> runs the staged form's arithmetic on these
+// operands, so on a shape both kernels take the results are bit-equal. A
+// __syncthreads() orders one stage's global stores before the next stage's
+// loads: the waves of a workgroup share one CU and its write-through L1.
+template <bool LIM, bool ACT_WS>
+__global__ void __launch_bounds__(512)
+tick_mlp_wide_kernel(MlpArgs a)
+{
+    int i = blockIdx.x;
+    int node = a.nodes[i];
+    int tid = threadIdx.x;
+    extern __shared__ float sm[];
+    float* W = a.params + (long)node * a.D;
+    float* wsrow = a.ws + (long)i * a.ws_row;
+    bool has_w2 = (a.mode == MODE_UPDATE_MERGE);
+    float* W2 = has_w2 ? wsrow : nullptr;
+    float* act;
+    if constexpr (ACT_WS) act = wsrow + (has_w2 ? a.D : 0);
+    else act = sm;
+    int bsmax = (a.bs == 0) ? a.Smax : min(a.bs, a.Smax);
+    int act_total = 0;
+    for (int l = 0; l < a.n_layers; ++l) act_total += a.layout[4 * l + 3];
+    float* grad = act + (long)bsmax * act_total;
+    int age = a.ages[node];
+
+    if (a.update_only) {
+        mlp_update<false, true>(a, node, W, act, grad, age);
+    } else {
+        for (int j = a.ptr[i]; j < a.ptr[i + 1]; ++j) {
+            int slot = a.dslots[j];
+            const float* srow = a.slots + (long)slot * a.D;
+            int sage = a.slot_ages[slot];
+            int md = (a.dmodes && a.dmodes[j]) ? MODE_PASS : a.mode;
+            if (md == MODE_MERGE_UPDATE) {
+                if constexpr (LIM) {
+                    lim_merge_row(lim_rule(age, sage, a.lim), W, srow, a.D);
+                } else {
+                    for (int e = tid; e < a.D; e += blockDim.x)
+                        W[e] = 0.5f * (W[e] + srow[e]);
+                }
+                age = max(age, sage);
+                __syncthreads();
+                mlp_update<false, true>(a, node, W, act, grad, age);
+            } else if (md == MODE_UPDATE) {
+                for (int e = tid; e < a.D; e += blockDim.x) W[e] = srow[e];
+                age = sage;
+                __syncthreads();
+                mlp_update<false, true>(a, node, W, act, grad, age);
+            } else if (md == MODE_UPDATE_MERGE) {
+                mlp_update<false, true>(a, node, W, act, grad, age);
+                for (int e = tid; e < a.D; e += blockDim.x) W2[e] = srow[e];
+                __syncthreads();
+                int age2 = sage;
+                mlp_update<false, true>(a, node, W2, act, grad, age2);
+                if constexpr (LIM) {
+                    lim_merge_row(lim_rule(age, age2, a.lim), W, W2, a.D);
+                } else {
+                    for (int e = tid; e < a.D; e += blockDim.x)
+                        W[e] = 0.5f * (W[e] + W2[e]);
+                }
+                age = max(age, age2);
+                __syncthreads();
+            } else {
+                for (int e = tid; e < a.D; e += blockDim.x) W[e] = srow[e];
+                age = sage;
+                __syncthreads();
+            }
+            int rs = a.rslots ? a.rslots[j] : -1;
+            if (rs >= 0) {
+                for (int e = tid; e < a.D; e += blockDim.x)
+                    a.slots[(long)rs * a.D + e] = W[e];
+                if (tid == 0) a.slot_ages[rs] = age;
+                __syncthreads();
+            }
+        }
+    }
     if (tid == 0) a.ages[node] = age;
 }
 
@@ -3184,7 +3315,55 @@ static Plan<KMeansArgs> kmeans_plan(const StateTensors& st, int64_t k,
 struct MlpGeom {
     size_t scratch;  // floats of activations + two grad buffers
     int threads;
+    // the same for tick_mlp_wide_kernel, which stages no input and computes
+    // no dX of layer 0: the layers' outputs + two buffers of the widest one
+    size_t wide_scratch;
+    int out_max;
 };
+
+constexpr size_t LDS_BUDGET = 160 * 1024;
+
+// floats of activations + two grad buffers for `rows` batch rows: with the
+// input staged and the buffers as wide as the widest layer side (the LDS
+// kernels), or without the input and by output widths alone (wide)
+static size_t mlp_scratch(int64_t rows, int64_t d_in, int64_t out_sum,
+                          int64_t width_max, bool wide)
+{
+    return (size_t)rows * ((wide ? 0 : d_in) + out_sum) +
+           2 * (size_t)rows * width_max;
+}
+
+// Which kernel serves a plain MLP tick whose LDS-resident plan needs
+// `lds_bytes`: tick_mlp_kernel whenever that fits, else the global-resident
+// tick_mlp_wide_kernel. GOSSIPY_MLP_WIDE=1 forces the wide kernel on any
+// shape (tests, A/B runs), =0 turns it off, which restores the budget error.
+static bool mlp_use_wide(size_t lds_bytes)
+{
+    const char* v = getenv("GOSSIPY_MLP_WIDE");
+    int knob = (v && *v) ? (atoi(v) != 0) : -1;
+    if (knob == 1) return true;
+    bool fits = lds_bytes <= LDS_BUDGET;
+    TORCH_CHECK(fits || knob != 0,
+        "mlp LDS budget exceeded (", lds_bytes, " B); shrink batch_size/hidden"
+        " (GOSSIPY_MLP_WIDE=0 has turned the global-resident kernel off)");
+    return !fits;
+}
+
+// Per-block rows of device memory for tick_mlp_wide_kernel, one buffer per
+// (device, stream): grown when a plan needs more, never shrunk, and reused
+// by every later plan, so a round loop allocates nothing after its first
+// launch. Never freed: the process's exit must not run into a torn-down
+// runtime.
+static float* mlp_wide_workspace(const torch::Device& dev, size_t floats)
+{
+    static auto* cache =
+        new std::map<std::pair<int, hipStream_t>, torch::Tensor>();
+    torch::Tensor& t = (*cache)[{(int)dev.index(), current_stream()}];
+    if (!t.defined() || (size_t)t.numel() < floats)
+        t = torch::empty({(int64_t)floats},
+                         torch::dtype(torch::kFloat32).device(dev));
+    return t.data_ptr<float>();
+}
 
 static MlpGeom mlp_fill(MlpArgs& a, const StateTensors& st,
                         torch::Tensor layout, int64_t n_layers, double lr,
@@ -3199,9 +3378,10 @@ static MlpGeom mlp_fill(MlpArgs& a, const StateTensors& st,
     fill_sgd(a, lr, wd, epochs, bs, mode);
     auto lay = layout.cpu();
     const int* Lh = lay.data_ptr<int>();
-    int act_sum = 0, act_max = Lh[2];
+    int act_sum = 0, act_max = Lh[2], out_max = 0;
     for (int l = 0; l < n_layers; ++l) {
         act_sum += Lh[4 * l + 3];
+        out_max = std::max(out_max, Lh[4 * l + 3]);
         act_max = std::max(act_max, Lh[4 * l + 3]);
         act_max = std::max(act_max, Lh[4 * l + 2]);
     }
@@ -3209,8 +3389,9 @@ static MlpGeom mlp_fill(MlpArgs& a, const StateTensors& st,
     a.d_in = Lh[2];
     int bsmax = batch_rows(bs, a.Smax);
     MlpGeom g;
-    g.scratch = (size_t)bsmax * (a.d_in + act_sum) +
-                2 * (size_t)bsmax * act_max;
+    g.scratch = mlp_scratch(bsmax, a.d_in, act_sum, act_max, false);
+    g.wide_scratch = mlp_scratch(bsmax, a.d_in, act_sum, out_max, true);
+    g.out_max = out_max;
     // block size: 8 waves when any GEMM stage has >= 8 MFMA tiles (halves
     // the sequential tile passes of the widest stage — e.g. dW [100,57] is
     // 28 tiles), else the default 4 waves
@@ -3240,13 +3421,58 @@ static Plan<MlpArgs> mlp_plan(
     // 2 grad buffers
     size_t w_slabs = (mode == MODE_UPDATE_MERGE) ? 2 : 1;
     L.smem = sizeof(float) * (w_slabs * (size_t)a.D + g.scratch);
-    TORCH_CHECK(L.smem <= 160 * 1024,
-        "mlp LDS budget exceeded (", L.smem, " B); shrink batch_size/hidden");
-    L.kernel = (merge_limit >= 0) ? tick_mlp_kernel<true>
-                                  : tick_mlp_kernel<false>;
+    bool lim = merge_limit >= 0;
     L.threads = g.threads;
     L.snap = {a.D, a.D, 0, 1};
+    if (!mlp_use_wide(L.smem)) {
+        L.kernel = lim ? tick_mlp_kernel<true> : tick_mlp_kernel<false>;
+        return L;
+    }
+    // wide: the rows live in device memory; the workspace row holds W2
+    // (UPDATE_MERGE only) and, when a batch's activations and gradients miss
+    // the LDS budget too, those. One row per node bounds every launch, as
+    // receivers are unique within one. No workspace without either.
+    a.act_max = g.out_max;
+    bool act_ws = sizeof(float) * g.wide_scratch > LDS_BUDGET;
+    L.smem = act_ws ? 0 : sizeof(float) * g.wide_scratch;
+    a.ws_row = (mode == MODE_UPDATE_MERGE ? a.D : 0) +
+               (act_ws ? (long)g.wide_scratch : 0);
+    size_t ws_bytes = sizeof(float) * (size_t)a.ws_row * st.params.size(0);
+    TORCH_CHECK(ws_bytes <= ((size_t)1 << 34),
+        "mlp wide workspace too large: ", st.params.size(0), " nodes x ",
+        a.ws_row, " floats (trained copy of the received model + a batch's"
+        " activations and gradients) = ", ws_bytes,
+        " B > 16 GiB; shrink batch_size/hidden");
+    a.ws = a.ws_row ? mlp_wide_workspace(st.params.device(),
+                                         (size_t)a.ws_row * st.params.size(0))
+                    : nullptr;
+    if (act_ws)
+        L.kernel = lim ? tick_mlp_wide_kernel<true, true>
+                       : tick_mlp_wide_kernel<false, true>;
+    else
+        L.kernel = lim ? tick_mlp_wide_kernel<true, false>
+                       : tick_mlp_wide_kernel<false, false>;
     return L;
+}
+
+// "lds" or "wide": the kernel mlp_plan picks for a plain MLP tick of layer
+// widths `dims` (d_in, hidden..., n_classes) on shards of stride Smax
+static std::string mlp_tick_path(std::vector<int64_t> dims, int64_t bs,
+                                 int64_t Smax, int64_t mode)
+{
+    TORCH_CHECK(dims.size() >= 2, "dims must hold d_in and n_classes");
+    int64_t D = 0, out_sum = 0, width_max = dims[0];
+    for (size_t l = 0; l + 1 < dims.size(); ++l) {
+        D += dims[l + 1] * dims[l] + dims[l + 1];
+        out_sum += dims[l + 1];
+        width_max = std::max(width_max, dims[l + 1]);
+    }
+    size_t w_slabs = (mode == MODE_UPDATE_MERGE) ? 2 : 1;
+    size_t lds = sizeof(float) *
+                 (w_slabs * (size_t)D +
+                  mlp_scratch(batch_rows(bs, (int)Smax), dims[0], out_sum,
+                              width_max, false));
+    return mlp_use_wide(lds) ? "wide" : "lds";
 }
 
 // Partitioned (part) or sampled compressed MLP. Checks the per-mode LDS
@@ -3292,7 +3518,9 @@ static Plan<MlpCompArgs> mlp_comp_plan(
              sizeof(int) * 2 * (size_t)c.P;
     TORCH_CHECK(L.smem <= 160 * 1024, what, " mlp LDS budget exceeded (",
                 L.smem, " B > 163840 B); shrink batch_size/hidden, or use"
-                " MERGE_UPDATE (the other modes hold a second model slab)");
+                " MERGE_UPDATE (the other modes hold a second model slab)."
+                " The global-resident wide kernel covers the plain MLP tick"
+                " only");
     L.kernel = part ? tick_mlp_comp_kernel<true> : tick_mlp_comp_kernel<false>;
     L.threads = g.threads;
     // snapshots copy one age per partition
@@ -3365,6 +3593,10 @@ void tick_mlp(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
 {
     auto L = mlp_plan({params, ages, slots, slot_ages, X, Y, counts},
                       layout, n_layers, lr, wd, epochs, bs, mode, merge_limit);
+    // receivers are unique within a launch (the wide kernel's workspace has
+    // one row per node)
+    TORCH_CHECK(nodes.size(0) <= params.size(0), "tick_mlp: ", nodes.size(0),
+                " receivers for ", params.size(0), " nodes");
     launch_tick(L, {nodes, recv_ptr, del_slots, reply_slots}, update_only,
                 &MlpArgs::dmodes, dmodes);
 }
@@ -3726,6 +3958,13 @@ static void run_round_mlp(
 {
     auto L = mlp_plan(c.st, layout, n_layers, lr, wd, epochs, bs, mode,
                       merge_limit);
+    // receivers are unique within a launch (the wide kernel's workspace has
+    // one row per node)
+    for (int t = 0; t < c.r.delta; ++t)
+        for (const int* p : {c.r.tptr[RT_RECV], c.r.tptr[RT_REP]})
+            TORCH_CHECK(p[t + 1] - p[t] <= c.st.params.size(0),
+                        "run_round_mlp: a launch of ", p[t + 1] - p[t],
+                        " receivers for ", c.st.params.size(0), " nodes");
     stream_round(L, c.r);
 }
 
@@ -3849,7 +4088,8 @@ void tick_pens_mlp(torch::Tensor params, torch::Tensor ages,
     size_t smem = sizeof(float) * ((size_t)p.m.D + g.scratch);
     TORCH_CHECK(smem + 2 * sizeof(int) * PENS_MAX_CAND <= 160 * 1024,
         "pens mlp LDS budget exceeded (", smem,
-        " B of dynamic LDS); shrink batch_size/hidden");
+        " B of dynamic LDS); shrink batch_size/hidden. The global-resident"
+        " wide kernel covers the plain MLP tick only");
     launch_kernel(tick_pens_mlp_kernel, n, g.threads, smem, current_stream(),
                   p);
 }
@@ -4649,6 +4889,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("tick_linear", &tick_linear, "fused merge + pegasos/adaline tick");
     m.def("tick_mlp", &tick_mlp,
           "fused merge + MLP SGD tick, merge_limit after mode");
+    m.def("mlp_tick_path", &mlp_tick_path,
+          "\"lds\" or \"wide\": the kernel tick_mlp / run_round_mlp run for"
+          " (dims, batch_size, Smax, mode)");
     m.def("run_round_logreg", round_entry(run_round_logreg),
           "whole-round executor, logreg family, merge_limit after mode",
           py::call_guard<py::gil_scoped_release>());
