@@ -1817,6 +1817,24 @@ class HIPBackend(TorchBackend):
             _MODE_ID[spec.mode],
         )
 
+    def logreg_tick_path(self, spec, data) -> str:
+        """Which kernel the plain logreg tick of ``spec`` runs on the shards
+        of ``data``: ``"lds"`` (the ``tick_logreg_*`` kernels: two model
+        slabs, the staged minibatch and its dz block in one workgroup's
+        160 KB of LDS) whenever that fits, else ``"wide"``
+        (``tick_logreg_wide_kernel``: one model row in LDS, the minibatch
+        streamed from the arena through MFMA tiles). ``GOSSIPY_LOGREG_WIDE=1``
+        forces ``"wide"``; with ``=0`` a shape past the budget raises the
+        budget error instead, as does a shape whose model row alone misses
+        the LDS. Partitioned, sampled and PENS logreg ticks have the LDS
+        kernels only."""
+        if spec.family != "logreg" or spec.n_parts > 0 or spec.sample_size > 0:
+            raise ValueError("logreg_tick_path: a plain LogRegSpec is required")
+        return self.ext.logreg_tick_path(
+            spec.d_in, spec.n_classes, spec.batch_size, data.x.shape[1],
+            _MODE_ID[spec.mode],
+        )
+
     def _family_call(self, spec, dev):
         """The one mapping from a spec to extension arguments. Returns
         ``(name, args, chan)``:

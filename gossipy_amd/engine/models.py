@@ -174,6 +174,18 @@ class LogRegSpec(_PartitionMixin):
     ``n_parts > 0`` switches the family to partitioned gossip
     (PartitionedTMH semantics: per-partition ages, age-weighted partition
     merge, gradient age-rescale — gossipy/model/handler.py:455-525).
+
+    On the GPU the plain tick (every mode, ``pass_through``, limited merge)
+    takes any shape whose model row fits LDS. While ``4 * (2 * D + rows *
+    d_in + rows * n_classes)`` bytes fit one workgroup's 160 KB of LDS
+    (``rows`` the largest minibatch) it runs the LDS-resident kernels; past
+    that, e.g. 784x10 with ``batch_size=32``, the wide kernel, which keeps
+    one model row and the ``rows * n_classes`` dz block in LDS and streams
+    the minibatch through MFMA tiles. ``HIPBackend.logreg_tick_path`` tells
+    which, and ``GOSSIPY_LOGREG_WIDE=1`` / ``=0`` force / forbid the wide one.
+    Still bound to the LDS budget: a model row that misses it alone (4096x16),
+    ``n_parts``, ``sample_size``, the PENS event and the opt-in cooperative
+    round, which raise a budget error past it.
     """
 
     d_in: int

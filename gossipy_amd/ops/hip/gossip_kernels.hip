@@ -50,6 +50,12 @@
 //                           more registers; picked host-side for launches
 //                           of at most one wave per SIMD, see
 //                           thin_launch_rows.
+//   tick_logreg_wide_kernel
+//                         — the logreg tick past the LDS budget (784x10 with
+//                           batches of 32 and up): one model row in LDS, the
+//                           batch streamed through double-buffered tiles,
+//                           forward and weight gradient on MFMA; picked
+//                           host-side, see logreg_use_wide.
 //   eval_metrics_kernel   — K13: accuracy / macro P-R-F1 / pairwise AUC of
 //                           R affine or margin models (or precomputed
 //                           scores) on a shared set or per-node shards.
@@ -152,6 +158,9 @@ struct LogregArgs {
     int d, k, Smax, D;
     float lr, wd;
     int epochs, bs, mode, update_only;
+    // tick_logreg_wide_kernel only: rows of a staging tile (0 = an LDS plan),
+    // log2 of its columns, and whether its rows start 16-byte aligned
+    int wide_rb, wide_lkp, wide_vec;
     int lim;  // limited-merge threshold L (LIM kernels only); last member
 };
 
@@ -2760,6 +2769,390 @@ tick_pens_mlp_kernel(PensMlpArgs p)
 }
 
 // ---------------------------------------------------------------------------
+// wide logreg tick: one workgroup of 256 threads per receiver row, for the
+// shapes whose two model slabs and staged batch miss the LDS budget of
+// tick_logreg_kernel (784x10 with batches of 32, 3072x10, 561x6 full-batch).
+//
+// LDS holds ONE model row W[D], the score / dz block [rows, k] and two
+// staging tiles of RB rows x KP columns; the batch is streamed from the data
+// arena through the tiles, once for the forward and once (L2-resident by
+// then) for the weight gradient. Both GEMMs run on v_mfma_f32_16x16x4_f32
+// with the fragment maps documented above mfma_kloop_padded.
+//
+//   forward   Z[m, k] = X·Wᵀ + b, row-block major. The class dimension is
+//             one zero-padded tile (k <= KMAX = 16), so the parallelism is
+//             in the RB/16 row tiles of a block and in K: wave w owns row
+//             tile w % RT and, of every panel, the 8-column chunks
+//             c = w / RT (mod 4 / RT). Its two accumulators live in
+//             registers across the panels of a row block; the partials of
+//             a row tile are then summed through LDS in wave order (no
+//             float atomics: a result depends on the shape alone).
+//   backward  dW[k, d] = dzᵀ·X, panel major. Of a panel's KP/16 column
+//             tiles wave w owns w, w + 4, ...; it accumulates over the row
+//             blocks (K = m) and applies W -= lr * (g + wd * W) to its own
+//             columns of the LDS row. The bias step is the column sum of dz.
+//
+// Tile t + 1 is loaded from the arena into registers before the MFMAs on
+// tile t and stored to the other buffer after them (issue_pre's register
+// double buffer), 16-byte loads when d % 4 == 0, scalar ones otherwise. A
+// tile row is KP + LRW_PAD floats: the stride is an odd multiple of 4 mod
+// 64, so the 16 rows x 4 columns of a forward operand read fall on 64
+// different banks, and the 4 rows x 16 columns of a backward one overlap in
+// at most 12 of them (a stride of KP would be a 16-way / 4-way conflict).
+//
+// UPDATE_MERGE has no second slab: the own trained model waits in its own
+// arena row, which is private to the block (a receiver is unique within a
+// launch), while the received model trains in LDS.
+// ---------------------------------------------------------------------------
+
+constexpr int LRW_THREADS = 256;
+constexpr int LRW_WAVES = LRW_THREADS / WAVE;
+constexpr int LRW_TILE = 4096;  // floats of a staging tile at the most
+constexpr int LRW_NV = LRW_TILE / LRW_THREADS / 4;  // float4 per thread
+constexpr int LRW_PAD = 20;
+constexpr int LRW_CTW = 4;  // column tiles per wave: KP <= 256
+
+// new code is built without packed fp32 math
+#define LRW_FN __attribute__((target("no-packed-fp32-ops")))
+
+struct LrwTile {
+    float4 v[LRW_NV];
+};
+
+// Registers <- the tile of batch rows row0.. and columns col0.. (zeros
+// outside the m x d batch). VEC: thread = 4 consecutive columns, else the
+// thread's 16 elements are LRW_THREADS apart; both read along d.
+template <bool VEC>
+DEV_INLINE LRW_FN void lrw_load(LrwTile& t, const float* Xb, int m, int d,
+                                int row0, int col0, int RB, int lkp)
+{
+    const int tid = threadIdx.x, n = RB << lkp;
+#pragma unroll
+    for (int u = 0; u < LRW_NV; ++u) {
+        if constexpr (VEC) {
+            int e = (tid + u * LRW_THREADS) << 2;
+            int r = row0 + (e >> lkp), c = col0 + (e & ((1 << lkp) - 1));
+            t.v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (e < n && r < m && c < d)
+                t.v[u] = *reinterpret_cast<const float4*>(Xb + (long)r * d + c);
+        } else {
+            float x[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                int e = tid + (u * 4 + q) * LRW_THREADS;
+                int r = row0 + (e >> lkp), c = col0 + (e & ((1 << lkp) - 1));
+                x[q] = (e < n && r < m && c < d) ? Xb[(long)r * d + c] : 0.f;
+            }
+            t.v[u] = make_float4(x[0], x[1], x[2], x[3]);
+        }
+    }
+}
+
+// the tile buffer `buf` (row stride LS) <- registers
+template <bool VEC>
+DEV_INLINE LRW_FN void lrw_store(const LrwTile& t, float* buf, int RB, int lkp,
+                                 int LS)
+{
+    const int tid = threadIdx.x, n = RB << lkp;
+#pragma unroll
+    for (int u = 0; u < LRW_NV; ++u) {
+        if constexpr (VEC) {
+            int e = (tid + u * LRW_THREADS) << 2;
+            if (e < n)
+                *reinterpret_cast<float4*>(
+                    buf + (e >> lkp) * LS + (e & ((1 << lkp) - 1))) = t.v[u];
+        } else {
+            const float x[4] = {t.v[u].x, t.v[u].y, t.v[u].z, t.v[u].w};
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                int e = tid + (u * 4 + q) * LRW_THREADS;
+                if (e < n) buf[(e >> lkp) * LS + (e & ((1 << lkp) - 1))] = x[q];
+            }
+        }
+    }
+}
+
+// zb[m, k] = Xb[m, d]·Wᵀ + b. `stage` is the two tiles; between two row
+// blocks, when no tile is live, its first 4 x 256 floats carry the waves'
+// partial sums. A barrier follows.
+template <bool VEC>
+DEV_INLINE LRW_FN void lrw_forward(const LogregArgs& a, const float* W,
+                                   const float* Xb, int m, float* zb,
+                                   float* stage)
+{
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+    const int li = lane & 15, lq = lane >> 4;
+    const int RB = a.wide_rb, lkp = a.wide_lkp, KP = 1 << lkp;
+    const int LS = KP + LRW_PAD;
+    const int RT = RB >> 4, KS = LRW_WAVES / RT;  // (1,4), (2,2) or (4,1)
+    const int rt = wave % RT, ks = wave / RT;
+    const int nP = (a.d + KP - 1) >> lkp, T = ((m + RB - 1) / RB) * nP;
+    const float* wr = W + li * a.d;  // lane's class row, read when li < k
+    LrwTile t;
+    lrw_load<VEC>(t, Xb, m, a.d, 0, 0, RB, lkp);
+    lrw_store<VEC>(t, stage, RB, lkp, LS);
+    __syncthreads();
+    f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+    f32x4_t acc2 = {0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < T; ++i) {
+        const int rb = i / nP, p = i - rb * nP;
+        if (i + 1 < T) {
+            int rb1 = (i + 1) / nP, p1 = (i + 1) - rb1 * nP;
+            lrw_load<VEC>(t, Xb, m, a.d, rb1 * RB, p1 << lkp, RB, lkp);
+        }
+        if (rb * RB + rt * 16 < m) {  // else the whole row tile is padding
+            const float* xt =
+                stage + (i & 1) * RB * LS + (rt * 16 + li) * LS + lq;
+            const int col = (p << lkp) + lq;
+            const int nch = (min(KP, a.d - (p << lkp)) + 7) >> 3;
+            for (int ch = ks; ch < nch; ch += KS) {
+                int k0 = ch << 3;
+                float av = xt[k0], av2 = xt[k0 + 4];
+                int c0 = col + k0, c1 = c0 + 4;
+                float bv = (li < a.k && c0 < a.d) ? wr[c0] : 0.f;
+                float bv2 = (li < a.k && c1 < a.d) ? wr[c1] : 0.f;
+                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc, 0, 0, 0);
+                acc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                    av2, bv2, acc2, 0, 0, 0);
+            }
+        }
+        if (p == nP - 1) {  // the row block is done: sum its K partials
+            __syncthreads();  // every wave has left both tiles
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                stage[wave * 256 + (lq * 4 + r) * 16 + li] = acc[r] + acc2[r];
+            __syncthreads();
+            for (int e = tid; e < RB * 16; e += LRW_THREADS) {
+                int row = e >> 4, cls = e & 15, s = rb * RB + row;
+                if (s < m && cls < a.k) {
+                    float z = W[a.k * a.d + cls];
+                    for (int q = 0; q < KS; ++q)
+                        z += stage[((row >> 4) + RT * q) * 256 +
+                                   (row & 15) * 16 + cls];
+                    zb[s * a.k + cls] = z;
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[r] = acc2[r] = 0.f;
+            __syncthreads();  // the next tile lands on the partials
+        }
+        if (i + 1 < T) lrw_store<VEC>(t, stage + ((i + 1) & 1) * RB * LS, RB, lkp, LS);
+        __syncthreads();
+    }
+}
+
+// W[k, d] -= lr * (dzbᵀ·Xb + wd * W) in place, b -= lr * colsum(dzb). A
+// barrier follows.
+template <bool VEC>
+DEV_INLINE LRW_FN void lrw_backward(const LogregArgs& a, float* W,
+                                    const float* Xb, int m, const float* dzb,
+                                    float* stage)
+{
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+    const int li = lane & 15, lq = lane >> 4;
+    const int RB = a.wide_rb, lkp = a.wide_lkp, KP = 1 << lkp;
+    const int LS = KP + LRW_PAD;
+    const int nRB = (m + RB - 1) / RB, nP = (a.d + KP - 1) >> lkp;
+    const int T = nP * nRB;
+    LrwTile t;
+    lrw_load<VEC>(t, Xb, m, a.d, 0, 0, RB, lkp);
+    lrw_store<VEC>(t, stage, RB, lkp, LS);
+    __syncthreads();
+    f32x4_t acc[LRW_CTW], acc2[LRW_CTW];
+#pragma unroll
+    for (int j = 0; j < LRW_CTW; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[j][r] = acc2[j][r] = 0.f;
+    for (int i = 0; i < T; ++i) {
+        const int p = i / nRB, rb = i - p * nRB;
+        if (i + 1 < T) {
+            int p1 = (i + 1) / nRB, rb1 = (i + 1) - p1 * nRB;
+            lrw_load<VEC>(t, Xb, m, a.d, rb1 * RB, p1 << lkp, RB, lkp);
+        }
+        const float* xt = stage + (i & 1) * RB * LS + lq * LS + li;
+        // column tiles of the panel that hold a column below d
+        const int nct = (min(KP, a.d - (p << lkp)) + 15) >> 4;
+        const int rows = min(RB, m - rb * RB);
+        for (int r0 = 0; r0 < rows; r0 += 8) {  // two K = 4 steps
+            int s = rb * RB + r0 + lq;
+            float av = (li < a.k && s < m) ? dzb[s * a.k + li] : 0.f;
+            float av2 = (li < a.k && s + 4 < m) ? dzb[(s + 4) * a.k + li] : 0.f;
+#pragma unroll
+            for (int j = 0; j < LRW_CTW; ++j) {
+                int ct = wave + j * LRW_WAVES;
+                if (ct < nct) {
+                    float bv = xt[r0 * LS + ct * 16];
+                    float bv2 = xt[(r0 + 4) * LS + ct * 16];
+                    acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                        av, bv, acc[j], 0, 0, 0);
+                    acc2[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                        av2, bv2, acc2[j], 0, 0, 0);
+                }
+            }
+        }
+        if (rb == nRB - 1) {  // the panel is done: step its columns
+#pragma unroll
+            for (int j = 0; j < LRW_CTW; ++j) {
+                int col = (p << lkp) + (wave + j * LRW_WAVES) * 16 + li;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    int cls = lq * 4 + r;
+                    if (wave + j * LRW_WAVES < nct && cls < a.k && col < a.d) {
+                        int e = cls * a.d + col;
+                        float g = acc[j][r] + acc2[j][r];
+                        if (a.wd != 0.f) g += a.wd * W[e];
+                        W[e] -= a.lr * g;
+                    }
+                    acc[j][r] = acc2[j][r] = 0.f;
+                }
+            }
+        }
+        if (i + 1 < T) lrw_store<VEC>(t, stage + ((i + 1) & 1) * RB * LS, RB, lkp, LS);
+        __syncthreads();
+    }
+    for (int e = tid; e < a.k; e += LRW_THREADS)
+        W[a.k * a.d + e] -= a.lr * col_chain(dzb + e, a.k, nullptr, 0, m);
+    __syncthreads();
+}
+
+// logreg_update on the LDS row W with the batch streamed: the same epochs,
+// batches and per-sample dLoss/dz formulas
+template <bool VEC>
+DEV_INLINE LRW_FN void lrw_update(const LogregArgs& a, int node, int c,
+                                  float* W, float* zb, float* stage, int& age)
+{
+    if (c == 0) return;
+    const int bsz = (a.bs == 0) ? c : min(a.bs, c);
+    const float* Xn = a.X + (long)node * a.Smax * a.d;
+    const float* Yn = a.Y + (long)node * a.Smax;
+    for (int ep = 0; ep < a.epochs; ++ep) {
+        for (int s0 = 0; s0 < c; s0 += bsz) {
+            const int m = min(bsz, c - s0);
+            const float* Xb = Xn + (long)s0 * a.d;
+            lrw_forward<VEC>(a, W, Xb, m, zb, stage);
+            // a = sigmoid(z); p = softmax(a); dz = (p - 1_y)/m * a*(1-a),
+            // in place over the sample's k scores; block-strided, so a
+            // batch may have more rows than the block has threads
+            for (int s = threadIdx.x; s < m; s += LRW_THREADS) {
+                float* zs = zb + s * a.k;
+                int yi = (int)Yn[s0 + s];
+                float amax = -1e30f;
+                for (int kk = 0; kk < a.k; ++kk) {
+                    float sg = 1.0f / (1.0f + __expf(-zs[kk]));
+                    zs[kk] = sg;
+                    amax = fmaxf(amax, sg);
+                }
+                float sum = 0.f;
+                for (int kk = 0; kk < a.k; ++kk) sum += __expf(zs[kk] - amax);
+                float inv = 1.0f / sum;
+                for (int kk = 0; kk < a.k; ++kk) {
+                    float sg = zs[kk];
+                    float pk = __expf(sg - amax);
+                    float g = pk * inv - (kk == yi ? 1.0f : 0.0f);
+                    zs[kk] = (g / m) * sg * (1.0f - sg);
+                }
+            }
+            __syncthreads();
+            lrw_backward<VEC>(a, W, Xb, m, zb, stage);
+            age += 1;
+        }
+    }
+}
+
+// Delivery semantics of logreg_process_node. The dynamic LDS is W[D], the
+// dz block and the tiles, each starting on a 16-byte boundary.
+template <bool LIM, bool VEC>
+DEV_INLINE LRW_FN void lrw_process_node(const LogregArgs& a, int i)
+{
+    const int node = a.nodes[i], tid = threadIdx.x;
+    const int c = a.counts[node];
+    extern __shared__ float4 lrw_sm[];
+    float* W = reinterpret_cast<float*>(lrw_sm);
+    const int bsmax = (a.bs == 0) ? a.Smax : min(a.bs, a.Smax);
+    float* zb = W + ((a.D + 3) & ~3);
+    float* stage = zb + ((bsmax * a.k + 3) & ~3);
+    float* prow = a.params + (long)node * a.D;
+
+    copy_row(W, prow, a.D);
+    __syncthreads();
+    int age = a.ages[node];
+    if (a.update_only) {
+        lrw_update<VEC>(a, node, c, W, zb, stage, age);
+    } else {
+        for (int j = a.ptr[i]; j < a.ptr[i + 1]; ++j) {
+            const int slot = a.dslots[j];
+            const float* srow = a.slots + (long)slot * a.D;
+            const int sage = a.slot_ages[slot];
+            const int md = (a.dmodes && a.dmodes[j]) ? MODE_PASS : a.mode;
+            if (md == MODE_MERGE_UPDATE) {
+                if constexpr (LIM) {
+                    lim_merge_row(lim_rule(age, sage, a.lim), W, srow, a.D);
+                } else {
+                    merge_rows(W, srow, a.D, [](float w, float s) {
+                        return 0.5f * (w + s);
+                    });
+                }
+                age = max(age, sage);
+                __syncthreads();
+                lrw_update<VEC>(a, node, c, W, zb, stage, age);
+            } else if (md == MODE_UPDATE) {
+                copy_row(W, srow, a.D);
+                age = sage;
+                __syncthreads();
+                lrw_update<VEC>(a, node, c, W, zb, stage, age);
+            } else if (md == MODE_UPDATE_MERGE) {
+                // the own trained model waits in its arena row while the
+                // received one trains in LDS; the merge reads it back
+                lrw_update<VEC>(a, node, c, W, zb, stage, age);
+                copy_row(prow, W, a.D);
+                __syncthreads();
+                copy_row(W, srow, a.D);
+                __syncthreads();
+                int age2 = sage;
+                lrw_update<VEC>(a, node, c, W, zb, stage, age2);
+                if constexpr (LIM) {
+                    // own = prow, received = W: the rule of lim_merge_row
+                    LimRule r = lim_rule(age, age2, a.lim);
+                    if (r.br == LIM_KEEP) {
+                        copy_row(W, prow, a.D);
+                    } else if (r.br == LIM_MIX) {
+                        merge_rows(W, prow, a.D, [&](float w, float own) {
+                            return r.m1 * own + r.m2 * w;
+                        });
+                    }
+                } else {
+                    merge_rows(W, prow, a.D, [](float w, float own) {
+                        return 0.5f * (own + w);
+                    });
+                }
+                age = max(age, age2);
+                __syncthreads();
+            } else {  // PASS
+                copy_row(W, srow, a.D);
+                age = sage;
+                __syncthreads();
+            }
+            const int rs = a.rslots ? a.rslots[j] : -1;
+            if (rs >= 0) {  // PUSH_PULL reply snapshot
+                copy_row(a.slots + (long)rs * a.D, W, a.D);
+                if (tid == 0) a.slot_ages[rs] = age;
+                __syncthreads();
+            }
+        }
+    }
+    __syncthreads();
+    copy_row(prow, W, a.D);
+    if (tid == 0) a.ages[node] = age;
+}
+
+template <bool LIM, bool VEC>
+__global__ LRW_FN void __launch_bounds__(LRW_THREADS)
+tick_logreg_wide_kernel(LogregArgs a)
+{
+    lrw_process_node<LIM, VEC>(a, blockIdx.x);
+}
+
+// ---------------------------------------------------------------------------
 // cooperative whole-round kernel (logreg family): the entire round — every
 // tick's snapshot and delivery batch — runs inside ONE kernel launch, with
 // grid.sync() as the tick barrier. Grids here are tiny (max batch ≈ a few
@@ -3175,6 +3568,80 @@ static int check_merge_limit(int64_t merge_limit)
 template <typename A> static A& events(A& a) { return a; }
 static MlpArgs& events(MlpCompArgs& c) { return c.m; }
 
+// bytes of LDS the tick_logreg_* kernels need: two model slabs, the staged
+// batch of `rows` rows and its dz block
+static size_t logreg_lds_bytes(int64_t d, int64_t k, int64_t rows)
+{
+    size_t D = (size_t)(k * d + k);
+    return sizeof(float) * (2 * D + (size_t)rows * d + (size_t)rows * k);
+}
+
+// Which kernel serves a plain logreg tick whose LDS-resident plan needs
+// `lds_bytes`: the tick_logreg_* kernels whenever that fits, else the
+// batch-streaming tick_logreg_wide_kernel. GOSSIPY_LOGREG_WIDE=1 forces the
+// wide kernel on any shape (tests, A/B runs), =0 turns it off, which restores
+// the budget error.
+static bool logreg_use_wide(size_t lds_bytes)
+{
+    const char* v = getenv("GOSSIPY_LOGREG_WIDE");
+    int knob = (v && *v) ? (atoi(v) != 0) : -1;
+    if (knob == 1) return true;
+    bool fits = lds_bytes <= 160 * 1024;
+    TORCH_CHECK(fits || knob != 0, "logreg LDS budget exceeded: ", lds_bytes);
+    return !fits;
+}
+
+// Staging tiles and dynamic LDS of tick_logreg_wide_kernel. The row block
+// RB covers the largest batch up to 64 rows, and a tile holds LRW_TILE floats
+// (16 per thread) unless d is narrower: 16 x 256, 32 x 128 or 64 x 64. When
+// the model row and the dz block leave less than two such tiles, KP halves
+// down to 32 and then RB down to 16; the floor, two tiles of 16 x 32
+// (6.5 KB with the padding), always holds the 4 x 256 forward partials.
+struct LogregWideGeom {
+    int RB, lkp;
+    size_t smem;
+};
+
+static LogregWideGeom logreg_wide_geom(int64_t d, int64_t k, int64_t rows)
+{
+    rows = std::max<int64_t>(rows, 1);
+    size_t D = (size_t)(k * d + k);
+    size_t fixed = sizeof(float) * (((D + 3) & ~(size_t)3) +
+                                    (((size_t)rows * k + 3) & ~(size_t)3));
+    LogregWideGeom g;
+    g.RB = rows <= 16 ? 16 : rows <= 32 ? 32 : 64;
+    g.lkp = 0;
+    while ((g.RB << g.lkp) < LRW_TILE) g.lkp += 1;
+    while (g.lkp > 5 && (1 << (g.lkp - 1)) >= d) g.lkp -= 1;
+    auto tiles = [&] {
+        return sizeof(float) * 2 * g.RB * ((size_t)(1 << g.lkp) + LRW_PAD);
+    };
+    while (fixed + tiles() > 160 * 1024 && (g.lkp > 5 || g.RB > 16)) {
+        if (g.lkp > 5) g.lkp -= 1; else g.RB /= 2;
+    }
+    g.smem = fixed + tiles();
+    TORCH_CHECK(g.smem <= 160 * 1024,
+        "logreg LDS budget exceeded (", g.smem, " B): the wide kernel keeps one"
+        " model row and one dz block in LDS (", D, " + ", rows * k,
+        " floats here) next to two staging tiles; shrink d_in, n_classes or"
+        " batch_size");
+    return g;
+}
+
+// "lds" or "wide": the kernel logreg_plan picks for a plain logreg tick on
+// shards of stride Smax (`mode` is accepted for symmetry with mlp_tick_path:
+// the logreg LDS plan has two slabs in every mode)
+static std::string logreg_tick_path(int64_t d, int64_t k, int64_t bs,
+                                    int64_t Smax, int64_t mode)
+{
+    (void)mode;
+    TORCH_CHECK(k <= KMAX, "n_classes > ", KMAX, " unsupported");
+    int rows = batch_rows(bs, (int)Smax);
+    if (!logreg_use_wide(logreg_lds_bytes(d, k, rows))) return "lds";
+    logreg_wide_geom(d, k, rows);  // raises when even the floor misses
+    return "wide";
+}
+
 static Plan<LogregArgs> logreg_plan(
     const StateTensors& st, int64_t d, int64_t k, double lr, double wd,
     int64_t epochs, int64_t bs, int64_t mode, int64_t merge_limit = -1)
@@ -3187,9 +3654,24 @@ static Plan<LogregArgs> logreg_plan(
     fill_sgd(a, lr, wd, epochs, bs, mode);
     a.lim = check_merge_limit(merge_limit);
     int bsmax = batch_rows(bs, a.Smax);
-    L.smem = sizeof(float) * (2 * a.D + (size_t)bsmax * a.d + (size_t)bsmax * a.k);
-    TORCH_CHECK(L.smem <= 160 * 1024, "logreg LDS budget exceeded: ", L.smem);
+    L.smem = logreg_lds_bytes(d, k, bsmax);
     bool lim = merge_limit >= 0;
+    L.snap = {a.D, a.D, 0, 1};
+    if (logreg_use_wide(L.smem)) {
+        LogregWideGeom g = logreg_wide_geom(d, k, bsmax);
+        a.wide_rb = g.RB; a.wide_lkp = g.lkp;
+        // 16-byte loads need every shard row to start on such a boundary
+        a.wide_vec = d % 4 == 0 && (uintptr_t)a.X % 16 == 0;
+        L.smem = g.smem;
+        if (a.wide_vec)
+            L.kernel = lim ? tick_logreg_wide_kernel<true, true>
+                           : tick_logreg_wide_kernel<false, true>;
+        else
+            L.kernel = lim ? tick_logreg_wide_kernel<true, false>
+                           : tick_logreg_wide_kernel<false, false>;
+        L.threads = LRW_THREADS;
+        return L;  // kernel_thin stays null: one instantiation per shape
+    }
     if (big_batch(bs, a.Smax)) {
         L.kernel = lim ? tick_logreg_lim_big_kernel : tick_logreg_big_kernel;
         L.kernel_thin = lim ? tick_logreg_lim_big_thin_kernel
@@ -3201,7 +3683,6 @@ static Plan<LogregArgs> logreg_plan(
     }
     L.threads = LOGREG_THREADS;
     L.thin_rows = thin_launch_rows(LOGREG_THREADS);
-    L.snap = {a.D, a.D, 0, 1};
     return L;
 }
 
@@ -3248,7 +3729,8 @@ static Plan<LogregPartArgs> logreg_part_plan(
         : sizeof(float) * (2 * a.D + (size_t)bsmax * a.d +
                            (size_t)bsmax * a.k) +
               sizeof(int) * 2 * a.P;
-    TORCH_CHECK(L.smem <= 160 * 1024, "partitioned logreg LDS budget exceeded: ", L.smem);
+    TORCH_CHECK(L.smem <= 160 * 1024, "partitioned logreg LDS budget exceeded: ",
+                L.smem, " (the wide kernel covers the plain logreg tick only)");
     L.kernel = tick_logreg_part_kernel;
     L.threads = 128;
     L.snap = {a.D, a.D, 0, a.P};
@@ -3269,7 +3751,8 @@ static Plan<LogregSampArgs> logreg_samp_plan(
     int bsmax = batch_rows(bs, a.Smax);
     L.smem = sizeof(float) * (3 * a.D + (size_t)bsmax * a.d +
                               (size_t)bsmax * a.k);
-    TORCH_CHECK(L.smem <= 160 * 1024, "sampled logreg LDS budget exceeded: ", L.smem);
+    TORCH_CHECK(L.smem <= 160 * 1024, "sampled logreg LDS budget exceeded: ",
+                L.smem, " (the wide kernel covers the plain logreg tick only)");
     L.kernel = big_batch(bs, a.Smax) ? tick_logreg_samp_kernel<true>
                                      : tick_logreg_samp_kernel<false>;
     L.threads = LOGREG_THREADS;
@@ -3911,8 +4394,9 @@ static void run_round_logreg(
     int64_t epochs, int64_t bs, int64_t mode, int64_t merge_limit)
 {
     auto L = logreg_plan(c.st, d, k, lr, wd, epochs, bs, mode, merge_limit);
-    // the single-workgroup round kernel has no limited-merge instantiation
-    if (merge_limit < 0 &&
+    // the single-workgroup round kernel embeds the LDS body and has no
+    // limited-merge instantiation
+    if (merge_limit < 0 && !L.a.wide_rb &&
         single_block_round(big_batch(bs, L.a.Smax)
                                ? coop_round_logreg_kernel<true>
                                : coop_round_logreg_kernel<false>,
@@ -4003,6 +4487,8 @@ static void run_round_coop_logreg(
     int64_t epochs, int64_t bs, int64_t mode, int64_t max_batch)
 {
     auto L = logreg_plan(rc.st, d, k, lr, wd, epochs, bs, mode);
+    TORCH_CHECK(!L.a.wide_rb, "cooperative logreg round: this shape misses the"
+                " LDS budget, and the wide kernel covers the plain tick only");
     CoopRoundArgs c = round_args<CoopRoundArgs>(L.a, rc.r);
     const void* kernel = big_batch(bs, L.a.Smax)
         ? (const void*)coop_round_logreg_kernel<true>
@@ -4055,7 +4541,8 @@ void tick_pens(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
     int bsmax = (bs == 0) ? a.Smax : std::min<int>(bs, a.Smax);
     size_t smem = sizeof(float) * (a.D + (size_t)bsmax * a.d +
                                    (size_t)bsmax * a.k);
-    TORCH_CHECK(smem <= 160 * 1024, "pens LDS budget exceeded: ", smem);
+    TORCH_CHECK(smem <= 160 * 1024, "pens LDS budget exceeded: ", smem,
+                " (the wide kernel covers the plain logreg tick only)");
     hipLaunchKernelGGL(big_batch(bs, a.Smax) ? tick_pens_kernel<true>
                                              : tick_pens_kernel<false>,
                        dim3(n), dim3(LOGREG_THREADS), smem, current_stream(),
@@ -4889,6 +5376,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("tick_linear", &tick_linear, "fused merge + pegasos/adaline tick");
     m.def("tick_mlp", &tick_mlp,
           "fused merge + MLP SGD tick, merge_limit after mode");
+    m.def("logreg_tick_path", &logreg_tick_path,
+          "\"lds\" or \"wide\": the kernel of a plain logreg tick (d, k, bs,"
+          " Smax, mode); host code, no GPU needed");
     m.def("mlp_tick_path", &mlp_tick_path,
           "\"lds\" or \"wide\": the kernel tick_mlp / run_round_mlp run for"
           " (dims, batch_size, Smax, mode)");
