@@ -7,9 +7,15 @@ plain MLP tick therefore runs the global-resident wide kernel
 the data arena); on a CPU-only machine the same script runs the TorchBackend
 oracle. Synthetic MNIST-shaped data (784 features, 10 classes).
 
-``--hidden`` sets the hidden widths, ``--mode`` the CreateModelMode. The
-script prints the tick path the configuration gets and the last global
-evaluation.
+Evaluation on per-node test shards (``--test-shards``) follows the same
+split: past the budget every evaluated node's own test split is forwarded by
+``eval_mlp_wide_kernel`` (a row-blocked MFMA forward that streams the
+weights through LDS) in place of a per-node Python loop.
+
+``--hidden`` sets the hidden widths, ``--mode`` the CreateModelMode,
+``--test-shards`` gives every node a test split of its own in place of the
+shared set. The script prints the tick path the configuration gets and the
+last global (or, with ``--test-shards``, local) evaluation.
 """
 
 import os
@@ -44,6 +50,11 @@ def main():
         help="hidden layer widths (none: a linear softmax classifier)",
     )
     ap.add_argument("--mode", choices=sorted(MODES), default="merge_update")
+    ap.add_argument(
+        "--test-shards", action="store_true",
+        help="evaluate every node on a test split of its own (a tenth of"
+             " its rows) instead of one shared set",
+    )
     args = ap.parse_args()
 
     device = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
@@ -51,10 +62,17 @@ def main():
     X, y = make_synthetic_classification((60 * n, d, k), seed=42, margin=2.0)
     idx = np.random.default_rng(42).permutation(len(y))
     cut = int(0.9 * len(y))
-    shards = [(X[s], y[s]) for s in np.array_split(idx[:cut], n)]
-    data = DataArena.from_shards(
-        shards, device, global_eval=(X[idx[cut:]], y[idx[cut:]])
-    )
+    if args.test_shards:
+        parts = np.array_split(idx, n)
+        cuts = [int(0.9 * len(s)) for s in parts]
+        shards = [(X[s[:c]], y[s[:c]]) for s, c in zip(parts, cuts)]
+        tests = [(X[s[c:]], y[s[c:]]) for s, c in zip(parts, cuts)]
+        data = DataArena.from_shards(shards, device, test_shards=tests)
+    else:
+        shards = [(X[s], y[s]) for s in np.array_split(idx[:cut], n)]
+        data = DataArena.from_shards(
+            shards, device, global_eval=(X[idx[cut:]], y[idx[cut:]])
+        )
     spec = MLPSpec(
         d_in=d, n_classes=k, hidden=tuple(args.hidden), lr=0.1,
         batch_size=32, mode=MODES[args.mode],
@@ -78,7 +96,13 @@ def main():
     sim.add_receiver(report)
     sim.init_nodes()
     sim.start(n_rounds=args.rounds)
-    print(f"final global eval: {report.get_evaluation(False)[-1][1]}")
+    if args.test_shards:
+        if sim.backend.name == "hip":
+            how = sim.backend.mlp_eval_path(spec, data.tx.shape[1])
+            print(f"local evaluation path: {how}")
+        print(f"final local eval: {report.get_evaluation(True)[-1][1]}")
+    else:
+        print(f"final global eval: {report.get_evaluation(False)[-1][1]}")
 
 
 if __name__ == "__main__":

@@ -1540,11 +1540,11 @@ class HIPBackend(TorchBackend):
         epilogue) when ``eval_mlp_tile`` says the model, the shard stride
         and 16 rows of forward scratch fit the LDS budget, and returns
         ``None`` otherwise, as under ``GOSSIPY_NO_MLP_EVAL_KERNEL=1`` (A/B
-        runs): the caller's per-node loop serves those. ``eval_mlp`` also
-        has a shared-set mode (empty ``eval_counts``, ``X`` ``[n, d_in]``);
-        it is not wired into :meth:`eval_metrics_fast` /
-        :meth:`eval_metrics_launch`, whose MLP scores still come from
-        :meth:`scores`."""
+        runs): :meth:`eval_local_wide` serves the shapes past the budget,
+        the caller's per-node loop what is left. ``eval_mlp`` also has a
+        shared-set mode (empty ``eval_counts``, ``X`` ``[n, d_in]``); it is
+        not wired into :meth:`eval_metrics_fast` /
+        :meth:`eval_metrics_launch`."""
         dev = state.params.device
         if spec.family == "mlp":
             if os.environ.get("GOSSIPY_NO_MLP_EVAL_KERNEL") == "1":
@@ -1577,6 +1577,54 @@ class HIPBackend(TorchBackend):
             )
         else:
             return None
+        return self._local_rows_to_dicts(out)
+
+    def _mlp_eval_wide_takes(self, spec, D, n_eval):
+        """Whether ``eval_mlp_wide`` is the evaluation of this MLP on test
+        shards of stride ``n_eval``: the shape is past ``eval_mlp``'s LDS
+        budget and ``eval_mlp_wide_fits`` takes it.
+        ``GOSSIPY_MLP_EVAL_WIDE=1`` adds the shapes that fit LDS (tests, A/B
+        runs); ``GOSSIPY_NO_MLP_EVAL_KERNEL=1`` turns it off."""
+        if (
+            spec.family != "mlp"
+            or os.environ.get("GOSSIPY_NO_MLP_EVAL_KERNEL") == "1"
+            or not self.ext.eval_mlp_wide_fits(list(spec.dims), n_eval)
+        ):
+            return False
+        if os.environ.get("GOSSIPY_MLP_EVAL_WIDE") == "1":
+            return True
+        return not self.ext.eval_mlp_tile(
+            D, spec.d_in, sum(spec.dims[1:]), n_eval
+        )
+
+    def eval_local_wide(self, state, spec, local_ids, tx, ty, tcounts):
+        """:meth:`eval_local_fast` for the MLP shapes past its LDS budget
+        (784-100-10): ``eval_mlp_wide`` forwards every evaluated node's
+        shard on a (row block, node) grid, streaming the weights through
+        LDS, and the metrics kernel reads the logits. Same metric dicts.
+        ``None`` when the family is not ``mlp``, ``eval_mlp_wide_fits`` is
+        false, the shape fits ``eval_mlp`` (unless
+        ``GOSSIPY_MLP_EVAL_WIDE=1``) or ``GOSSIPY_NO_MLP_EVAL_KERNEL=1``."""
+        if not self._mlp_eval_wide_takes(
+            spec, state.params.shape[1], tx.shape[1]
+        ):
+            return None
+        dev = state.params.device
+        out = self.ext.eval_mlp_wide(
+            state.params,
+            local_ids.to(dev, torch.int32),
+            tx,
+            ty,
+            self._mlp_layout(spec, dev),
+            len(spec.dims) - 1,
+            tcounts,
+        )
+        return self._local_rows_to_dicts(out)
+
+    @staticmethod
+    def _local_rows_to_dicts(out):
+        """Metric dicts of the ``[R, 5]`` rows of a per-node evaluation,
+        without the rows of empty shards."""
         vals = out.cpu().numpy()
         res = []
         for row in vals:
@@ -1669,8 +1717,10 @@ class HIPBackend(TorchBackend):
         round's compute (the collect usually finds the event already
         signalled). Affine/margin families score inside the kernel;
         MLP/torchmod run their (batched) forward first and feed the
-        precomputed scores to the same metrics epilogue. Returns ``None``
-        for unsupported families."""
+        precomputed scores to the same metrics epilogue (``eval_mlp_wide``
+        has a shared-set mode, which measured slower than this at
+        784-100-10, profiles/mlp_wide_eval.md, and is not wired in). Returns
+        ``None`` for unsupported families."""
         if (
             spec.family in ("logreg", "pegasos", "adaline")
             and gx.shape[0] <= 2048
@@ -1744,7 +1794,8 @@ class HIPBackend(TorchBackend):
         conventions); argmax/AUC on raw affine scores — the reference's
         sigmoid is monotonic so predictions and ranks are identical.
         MLP/torchmod feed their batched forward's scores to the same
-        kernel epilogue."""
+        kernel epilogue (not ``eval_mlp_wide``'s shared-set mode, see
+        :meth:`eval_metrics_launch`)."""
         if (
             spec.family in ("logreg", "pegasos", "adaline")
             and gx.shape[0] <= 2048
@@ -1816,6 +1867,25 @@ class HIPBackend(TorchBackend):
             list(spec.dims), spec.batch_size, data.x.shape[1],
             _MODE_ID[spec.mode],
         )
+
+    def mlp_eval_path(self, spec, n_eval) -> str:
+        """Which code the runner evaluates the MLP of ``spec`` with on
+        per-node test shards of stride ``n_eval``: ``"lds"``
+        (``eval_mlp_kernel``: model row and forward scratch in LDS),
+        ``"wide"`` (``eval_mlp_wide_kernel``: past that budget, weights
+        streamed through LDS) or ``"torch"`` (the per-node loop: neither
+        takes the shape, or ``GOSSIPY_NO_MLP_EVAL_KERNEL=1``)."""
+        if (
+            os.environ.get("GOSSIPY_NO_MLP_EVAL_KERNEL") != "1"
+            and spec.n_classes <= self.ext.EVAL_KMAX
+            and self.ext.eval_mlp_tile(
+                spec.D, spec.d_in, sum(spec.dims[1:]), n_eval
+            )
+        ):
+            return "lds"
+        if self._mlp_eval_wide_takes(spec, spec.D, n_eval):
+            return "wide"
+        return "torch"
 
     def logreg_tick_path(self, spec, data) -> str:
         """Which kernel the plain logreg tick of ``spec`` runs on the shards

@@ -258,10 +258,12 @@ class MLPSpec(_PartitionMixin):
     runs the LDS-resident kernel; past that, e.g. 784-100-10, the
     global-resident wide kernel, which returns the same bits on a shape both
     take. ``HIPBackend.mlp_tick_path`` tells which, and
-    ``GOSSIPY_MLP_WIDE=1`` / ``=0`` force / forbid the wide one. Still bound
-    to the LDS budget: ``n_parts``, ``sample_size`` and the PENS event, which
-    raise a budget error past it, and the one-launch per-node evaluation,
-    which falls back to the per-node loop.
+    ``GOSSIPY_MLP_WIDE=1`` / ``=0`` force / forbid the wide one. Evaluation
+    follows the same split: ``eval_mlp`` while the row and 16 rows of forward
+    scratch fit LDS, ``eval_mlp_wide`` past that, on per-node test shards of
+    at most 2048 rows (a shared set scores through torch). Still bound to the LDS budget:
+    ``n_parts``, ``sample_size`` and the PENS event, which raise a budget
+    error past it.
     """
 
     d_in: int

@@ -739,6 +739,13 @@ class BatchedGossipSimulator(SimulationEventSender):
                     self.state, self.spec, local_ids,
                     self.data.tx, self.data.ty, self.data.tcounts,
                 )
+            wide_local = getattr(self.backend, "eval_local_wide", None)
+            if got_local is None and wide_local is not None:
+                # the MLP shapes past the LDS budget of the kernel above
+                got_local = wide_local(
+                    self.state, self.spec, local_ids,
+                    self.data.tx, self.data.ty, self.data.tcounts,
+                )
             if got_local is not None:
                 results_local = got_local
         if self.data.tx is not None and len(mine) and not results_local:

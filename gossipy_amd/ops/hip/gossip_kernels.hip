@@ -62,6 +62,11 @@
 //   eval_mlp_kernel       — K13 for the MLP family: mlp_forward over the
 //                           evaluation rows, then eval_metrics_kernel's
 //                           epilogue (eval_epilogue), in one launch.
+//   eval_mlp_wide_kernel  — the MLP evaluation forward past the LDS budget
+//                           (784-100-10): row-blocked over a (row block,
+//                           model) grid, every layer streamed through LDS in
+//                           K panels on MFMA, head logits to a workspace that
+//                           eval_metrics_kernel reads in scores mode.
 //
 // Models are tiny (57x2 logreg ... few-hundred-wide MLPs); per-launch work
 // is launch-latency bound, so kernels are built to let ONE launch cover all
@@ -2242,7 +2247,9 @@ struct EvalArgs {
     // arenas, eval_counts[node] gives the node's row count
     const int* eval_counts;
     // precomputed-scores mode (MLP/torchmod: any family whose forward ran
-    // elsewhere): [R, n_eval, k] raw scores; skips the scoring GEMM stage
+    // elsewhere): [R, n_eval, k] raw scores; skips the scoring GEMM stage.
+    // With nodes and eval_counts set (eval_mlp_wide on per-node shards) row
+    // r's labels are shard nodes[r]'s and its first eval_counts rows count.
     const float* scores;
 };
 
@@ -2395,7 +2402,9 @@ eval_metrics_kernel(EvalArgs a)
 
     if (a.scores) {
         // precomputed scores: just argmax + confusion + score staging
-        const float* zs = a.scores + (long)r * n_e * (a.is_margin ? 1 : a.k);
+        // the score row stride is a.n_eval: n_e is a shard's live count
+        const float* zs =
+            a.scores + (long)r * a.n_eval * (a.is_margin ? 1 : a.k);
         for (int sidx = tid; sidx < n_e; sidx += blockDim.x) {
             int pred, yt;
             float sc1;
@@ -3153,6 +3162,273 @@ tick_logreg_wide_kernel(LogregArgs a)
 }
 
 // ---------------------------------------------------------------------------
+// wide MLP evaluation forward: head logits Z[R, S, k] of R models on their
+// evaluation rows, for models whose row misses the LDS of eval_mlp_kernel
+// (784-100-10: 318 KB). eval_metrics_kernel in scores mode turns Z into the
+// metric rows in a second launch.
+//
+// The grid is (ceil(S / RB), R): block (c, r) forwards rows [c*RB, c*RB+RB)
+// of node nodes[r], so the rows of one model spread over many CUs (the LDS
+// kernel is one block per model). Addressing as EvalMlpArgs: per-node shards
+// (eval_counts set, X [n_local, S, d_in] indexed by the local row id) or one
+// shared set (X [S, d_in]). A block at or past the node's live count leaves
+// at once; rows past the count are never read.
+//
+// No weight matrix is ever whole in LDS. Every layer is a GEMM streamed over
+// K in panels of EMW_KP columns: the [<= EMW_CG outputs] x KP panel of W_l
+// goes through two staging tiles, and for layer 0 so does the RB x KP panel
+// of X; layers l >= 1 take their A operand from the activation buffer the
+// layer before wrote. Panel p + 1 is loaded into registers before the MFMAs
+// on panel p and stored to the other tile after them. X is read with 16-byte
+// loads when d_in % 4 == 0 (template VEC), W_l when its row and the layer's
+// offset allow it (decided per block and layer: D is rarely a multiple of 4).
+//
+// Work split of the 4 waves, RT = RB / 16 row tiles: wave w owns row tile
+// w % RT and, of a pass's EMW_CG / 16 = 8 column tiles, those with
+// ct % (4 / RT) == w / RT: 8, 4 or 2 accumulators that stay in registers
+// across the panels. A layer of more than EMW_CG outputs takes several
+// passes, each streaming the (L2-resident) input again. Bias and ReLU are
+// applied to the accumulators; hidden layers go to one of two ping-pong
+// activation buffers of RB rows, the head straight to Z.
+//
+// Bank arithmetic (64 banks of 4 bytes). Both operands are read as 16 rows
+// x 4 consecutive columns: lane l takes A[l & 15][k0 + (l >> 4)] and, W_l
+// being [out, in] row-major, B as W[c + (l & 15)][k0 + (l >> 4)]. With a row
+// stride LS the bank is ((l & 15) * LS + (l >> 4)) mod 64. LS = KP + 4 = 36
+// = 4 * 9, and 9 is odd, so (l & 15) * 9 mod 16 runs over all 16 residues and
+// (l & 15) * LS mod 64 over the 16 multiples of 4; adding l >> 4 in 0..3
+// gives 64 different banks. A stride of KP = 32 would put rows 0, 2, 4, ...
+// on one bank (8-way). The activation stride is the widest hidden layer
+// rounded up to 8, plus 4: again 4 * odd. The epilogue stores rows
+// (l >> 4) * 4 + r, columns l & 15: (l >> 4) * 4 * AS mod 64 is
+// (l >> 4) * 16 * odd mod 64, the 4 multiples of 16, plus 0..15: 64 banks.
+// ---------------------------------------------------------------------------
+
+constexpr int EMW_THREADS = 256;
+constexpr int EMW_KP = 32;            // columns of a K panel
+constexpr int EMW_LS = EMW_KP + 4;    // row stride of a staging tile
+constexpr int EMW_CG = 128;           // outputs of a column-group pass
+constexpr int EMW_WNV = EMW_CG * EMW_KP / EMW_THREADS / 4;  // float4 / thread
+
+struct EvalMlpWideArgs {
+    const float* params;     // [n_local, D]
+    const int* nodes;        // [R] local row ids
+    const float* X;          // [n_local, S, d_in] or [S, d_in]
+    const int* layout;       // [n_layers][4] = (w_off, b_off, in, out)
+    const int* eval_counts;  // [n_local], or null: shared set
+    float* Z;                // [R, S, k] head logits
+    int n_layers, D, d_in, S, k;
+    int act_stride;          // row stride of an activation buffer
+    int w_aligned;           // params is 16-byte aligned
+};
+
+// Registers <- `rows` x EMW_KP floats of the row-major matrix at src (row
+// stride ld), from column col0 on; zeros, and no read, outside its nrows x
+// ncols. VEC: thread = 4 consecutive columns, else its elements are
+// EMW_THREADS apart; both read along the rows.
+template <int NV, bool VEC>
+DEV_INLINE LRW_FN void emw_load(float4 (&v)[NV], const float* src, int ld,
+                                int nrows, int ncols, int col0, int rows)
+{
+    const int tid = threadIdx.x, n = rows * EMW_KP;
+#pragma unroll
+    for (int u = 0; u < NV; ++u) {
+        if constexpr (VEC) {
+            int e = (tid + u * EMW_THREADS) << 2;
+            int r = e / EMW_KP, c = col0 + (e & (EMW_KP - 1));
+            v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (e < n && r < nrows && c < ncols)
+                v[u] = *reinterpret_cast<const float4*>(src + (long)r * ld + c);
+        } else {
+            float x[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                int e = tid + (u * 4 + q) * EMW_THREADS;
+                int r = e / EMW_KP, c = col0 + (e & (EMW_KP - 1));
+                x[q] = (e < n && r < nrows && c < ncols)
+                           ? src[(long)r * ld + c] : 0.f;
+            }
+            v[u] = make_float4(x[0], x[1], x[2], x[3]);
+        }
+    }
+}
+
+// the staging tile `buf` (rows x EMW_LS) <- registers
+template <int NV, bool VEC>
+DEV_INLINE LRW_FN void emw_store(const float4 (&v)[NV], float* buf, int rows)
+{
+    const int tid = threadIdx.x, n = rows * EMW_KP;
+#pragma unroll
+    for (int u = 0; u < NV; ++u) {
+        if constexpr (VEC) {
+            int e = (tid + u * EMW_THREADS) << 2;
+            if (e < n)
+                *reinterpret_cast<float4*>(
+                    buf + (e / EMW_KP) * EMW_LS + (e & (EMW_KP - 1))) = v[u];
+        } else {
+            const float x[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                int e = tid + (u * 4 + q) * EMW_THREADS;
+                if (e < n)
+                    buf[(e / EMW_KP) * EMW_LS + (e & (EMW_KP - 1))] = x[q];
+            }
+        }
+    }
+}
+
+// float4 per thread of an RB x EMW_KP input panel (RB = 16 fills half a one)
+template <int RB>
+constexpr int emw_xnv()
+{
+    return RB * EMW_KP / EMW_THREADS / 4 > 0 ? RB * EMW_KP / EMW_THREADS / 4 : 1;
+}
+
+// Panel pn of a GEMM into registers: wrows x EMW_KP of the pass's weight
+// rows at Wp (wvalid of them exist) and, where Xl is set (layer 0), RB x
+// EMW_KP of the block's m input rows. vw: 16-byte loads of W are possible.
+
+template <int RB, bool VEC>
+DEV_INLINE LRW_FN void emw_load_panel(float4 (&wreg)[EMW_WNV],
+                                      float4 (&xreg)[emw_xnv<RB>()], bool vw,
+                                      const float* Wp, int fin, int wvalid,
+                                      int wrows, const float* Xl, int d_in,
+                                      int m, int pn)
+{
+    if (vw)
+        emw_load<EMW_WNV, true>(wreg, Wp, fin, wvalid, fin, pn * EMW_KP, wrows);
+    else
+        emw_load<EMW_WNV, false>(wreg, Wp, fin, wvalid, fin, pn * EMW_KP, wrows);
+    if (Xl)
+        emw_load<emw_xnv<RB>(), VEC>(xreg, Xl, d_in, m, d_in, pn * EMW_KP, RB);
+}
+
+// the registers of a panel to the staging tiles wt and (layer 0) xt
+template <int RB, bool VEC>
+DEV_INLINE LRW_FN void emw_store_panel(const float4 (&wreg)[EMW_WNV],
+                                       const float4 (&xreg)[emw_xnv<RB>()],
+                                       bool vw, float* wt, int wrows, float* xt)
+{
+    if (vw)
+        emw_store<EMW_WNV, true>(wreg, wt, wrows);
+    else
+        emw_store<EMW_WNV, false>(wreg, wt, wrows);
+    if (xt) emw_store<emw_xnv<RB>(), VEC>(xreg, xt, RB);
+}
+
+template <int RB, bool VEC>
+__global__ LRW_FN void __launch_bounds__(EMW_THREADS)
+eval_mlp_wide_kernel(EvalMlpWideArgs p)
+{
+    constexpr int RT = RB / 16;          // row tiles of the block
+    constexpr int CS = 4 / RT;           // waves that share a row tile
+    constexpr int NT = EMW_CG / 16 / CS; // column tiles of a wave per pass
+    constexpr int XNV = emw_xnv<RB>();
+    const int r = blockIdx.y, node = p.nodes[r];
+    const int row0 = blockIdx.x * RB;
+    int live = p.S;
+    const float* Xb = p.X;
+    if (p.eval_counts) {
+        live = min(p.eval_counts[node], p.S);
+        Xb += (long)node * p.S * p.d_in;
+    }
+    if (row0 >= live) return;
+    const int m = min(RB, live - row0);  // live rows of the block
+    Xb += (long)row0 * p.d_in;
+    float* Zb = p.Z + ((long)r * p.S + row0) * p.k;
+    const float* prow = p.params + (long)node * p.D;
+
+    extern __shared__ float sm[];
+    float* wst = sm;                              // 2 x EMW_CG x EMW_LS
+    float* xst = wst + 2 * EMW_CG * EMW_LS;       // 2 x RB x EMW_LS
+    float* act = xst + 2 * RB * EMW_LS;           // 2 x RB x act_stride
+    const int AS = p.act_stride;
+
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+    const int li = lane & 15, lq = lane >> 4;
+    const int rt = wave % RT, cs = wave / RT;
+
+    for (int l = 0; l < p.n_layers; ++l) {
+        const int w_off = p.layout[4 * l], b_off = p.layout[4 * l + 1];
+        const int fin = p.layout[4 * l + 2], fout = p.layout[4 * l + 3];
+        const bool head = l == p.n_layers - 1;
+        const float* Wl = prow + w_off;
+        const float* cur = act + ((l + 1) & 1) * RB * AS;  // layer l - 1's
+        float* nxt = act + (l & 1) * RB * AS;
+        const bool vw = p.w_aligned && !(fin & 3) &&
+                        !(((long)node * p.D + w_off) & 3);
+        const int nP = (fin + EMW_KP - 1) / EMW_KP;
+        for (int c0 = 0; c0 < fout; c0 += EMW_CG) {
+            const int wvalid = min(EMW_CG, fout - c0);
+            const int wrows = (wvalid + 15) & ~15, nct = wrows >> 4;
+            const float* Wp = Wl + (long)c0 * fin;
+            float4 wreg[EMW_WNV], xreg[XNV];
+            const float* Xl = l == 0 ? Xb : nullptr;  // layer 0 stages X too
+            f32x4_t acc[NT];
+#pragma unroll
+            for (int j = 0; j < NT; ++j)
+                for (int q = 0; q < 4; ++q) acc[j][q] = 0.f;
+            emw_load_panel<RB, VEC>(wreg, xreg, vw, Wp, fin, wvalid, wrows, Xl,
+                                    p.d_in, m, 0);
+            emw_store_panel<RB, VEC>(wreg, xreg, vw, wst, wrows, Xl ? xst : nullptr);
+            __syncthreads();
+            for (int pn = 0; pn < nP; ++pn) {
+                if (pn + 1 < nP)
+                    emw_load_panel<RB, VEC>(wreg, xreg, vw, Wp, fin, wvalid,
+                                            wrows, Xl, p.d_in, m, pn + 1);
+                const float* wt =
+                    wst + (pn & 1) * EMW_CG * EMW_LS + li * EMW_LS + lq;
+                const float* xt =
+                    xst + (pn & 1) * RB * EMW_LS + (rt * 16 + li) * EMW_LS + lq;
+                const float* at = cur + (rt * 16 + li) * AS + pn * EMW_KP + lq;
+                const int kleft = fin - pn * EMW_KP;  // live columns
+                const int kend = min(EMW_KP, (kleft + 3) & ~3);
+                for (int kk = 0; kk < kend; kk += 4) {
+                    // the X tile is zero past d_in; the activation buffer
+                    // holds stale floats there
+                    float av = l == 0 ? xt[kk]
+                                      : (kk + lq < kleft ? at[kk] : 0.f);
+#pragma unroll
+                    for (int j = 0; j < NT; ++j) {
+                        int ct = cs + j * CS;
+                        if (ct < nct)
+                            acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                                av, wt[ct * 16 * EMW_LS + kk], acc[j], 0, 0, 0);
+                    }
+                }
+                if (pn + 1 < nP)
+                    emw_store_panel<RB, VEC>(
+                        wreg, xreg, vw,
+                        wst + ((pn + 1) & 1) * EMW_CG * EMW_LS, wrows,
+                        Xl ? xst + ((pn + 1) & 1) * RB * EMW_LS : nullptr);
+                __syncthreads();
+            }
+            // accumulator lane l, register q: row (l >> 4) * 4 + q, column
+            // l & 15 of the tile
+#pragma unroll
+            for (int j = 0; j < NT; ++j) {
+                int col = c0 + (cs + j * CS) * 16 + li;
+                if (col < fout) {
+                    float b = prow[b_off + col];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        int row = rt * 16 + lq * 4 + q;
+                        float v = acc[j][q] + b;
+                        if (!head)
+                            nxt[row * AS + col] = fmaxf(v, 0.f);
+                        else if (row < m)
+                            Zb[(long)row * p.k + col] = v;
+                    }
+                }
+            }
+            // the next pass's first store lands on tile 0, which every wave
+            // left at the loop's last barrier; nxt is read after the next
+            // layer's first barrier
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // cooperative whole-round kernel (logreg family): the entire round — every
 // tick's snapshot and delivery batch — runs inside ONE kernel launch, with
 // grid.sync() as the tick barrier. Grids here are tiny (max batch ≈ a few
@@ -3395,12 +3671,12 @@ static const int* iptr(const torch::Tensor& t)
 // Launch of a kernel held as a pointer (a plan picks it at run time):
 // hipLaunchKernel is the call a `<<<>>>` launch makes underneath.
 template <typename Args>
-static void launch_kernel(void (*kernel)(Args), int grid, int block,
+static void launch_kernel(void (*kernel)(Args), dim3 grid, int block,
                           size_t smem, hipStream_t s, Args& a)
 {
     void* kargs[] = {&a};
-    hipError_t err = hipLaunchKernel((const void*)kernel, dim3(grid),
-                                     dim3(block), kargs, smem, s);
+    hipError_t err = hipLaunchKernel((const void*)kernel, grid, dim3(block),
+                                     kargs, smem, s);
     TORCH_CHECK(err == hipSuccess, "kernel launch failed: ",
                 hipGetErrorString(err));
 }
@@ -4683,9 +4959,19 @@ static int64_t eval_mlp_tile(int64_t D, int64_t d_in, int64_t act_total,
     return std::min<int64_t>({room, n_eval, 512});
 }
 
-torch::Tensor eval_mlp(torch::Tensor params, torch::Tensor nodes,
-                       torch::Tensor X, torch::Tensor Y, torch::Tensor layout,
-                       int64_t n_layers, torch::Tensor eval_counts)
+// What eval_mlp and eval_mlp_wide read off their (checked) arguments.
+struct EvalMlpShape {
+    bool per_node;
+    int64_t D, d_in, act_total, max_hidden, k, n_eval;
+};
+
+static EvalMlpShape eval_mlp_check(const torch::Tensor& params,
+                                   const torch::Tensor& nodes,
+                                   const torch::Tensor& X,
+                                   const torch::Tensor& Y,
+                                   const torch::Tensor& layout,
+                                   int64_t n_layers,
+                                   const torch::Tensor& eval_counts)
 {
     CHECK_DEV(params); CHECK_DEV(nodes); CHECK_DEV(X); CHECK_DEV(Y);
     CHECK_DEV(layout);
@@ -4699,39 +4985,51 @@ torch::Tensor eval_mlp(torch::Tensor params, torch::Tensor nodes,
     TORCH_CHECK(params.dim() == 2, "params must be [n_local, D]");
     TORCH_CHECK(n_layers >= 1 && layout.numel() == 4 * n_layers,
                 "mlp layout must hold n_layers x (w_off, b_off, in, out)");
-    bool per_node = eval_counts.defined() && eval_counts.numel();
-    int64_t D = params.size(1);
+    EvalMlpShape g{};
+    g.per_node = eval_counts.defined() && eval_counts.numel();
+    g.D = params.size(1);
     auto lay = layout.cpu();
     const int* Lh = lay.data_ptr<int>();
-    int64_t d_in = Lh[2], act_total = 0;
+    g.d_in = Lh[2];
     for (int l = 0; l < n_layers; ++l) {
         int64_t w_off = Lh[4 * l], b_off = Lh[4 * l + 1];
         int64_t fin = Lh[4 * l + 2], fout = Lh[4 * l + 3];
         TORCH_CHECK(fin >= 1 && fout >= 1 && w_off >= 0 && b_off >= 0 &&
-                        w_off + fin * fout <= D && b_off + fout <= D &&
-                        fin == (l ? Lh[4 * l - 1] : d_in),
-                    "mlp layout does not fit a params row of ", D);
-        act_total += fout;
+                        w_off + fin * fout <= g.D && b_off + fout <= g.D &&
+                        fin == (l ? Lh[4 * l - 1] : g.d_in),
+                    "mlp layout does not fit a params row of ", g.D);
+        g.act_total += fout;
+        if (l < n_layers - 1) g.max_hidden = std::max(g.max_hidden, fout);
     }
-    int64_t k = Lh[4 * (n_layers - 1) + 3];
-    TORCH_CHECK(k <= EVAL_KMAX, "n_classes > ", EVAL_KMAX, " unsupported");
-    int64_t n_eval;
-    if (per_node) {
+    g.k = Lh[4 * (n_layers - 1) + 3];
+    TORCH_CHECK(g.k <= EVAL_KMAX, "n_classes > ", EVAL_KMAX, " unsupported");
+    if (g.per_node) {
         CHECK_DEV(eval_counts);
         TORCH_CHECK(eval_counts.scalar_type() == torch::kInt32,
                     "eval_counts must be int32");
-        TORCH_CHECK(X.dim() == 3 && X.size(2) == d_in && Y.dim() == 2 &&
+        TORCH_CHECK(X.dim() == 3 && X.size(2) == g.d_in && Y.dim() == 2 &&
                         Y.size(0) == X.size(0) && Y.size(1) == X.size(1) &&
                         eval_counts.numel() == X.size(0),
                     "per-node mode: X [n_local, S, d_in], Y [n_local, S],"
                     " eval_counts [n_local]");
-        n_eval = X.size(1);
+        g.n_eval = X.size(1);
     } else {
-        TORCH_CHECK(X.dim() == 2 && X.size(1) == d_in &&
+        TORCH_CHECK(X.dim() == 2 && X.size(1) == g.d_in &&
                         Y.numel() == X.size(0),
                     "shared-set mode: X [n, d_in], Y [n]");
-        n_eval = X.size(0);
+        g.n_eval = X.size(0);
     }
+    return g;
+}
+
+torch::Tensor eval_mlp(torch::Tensor params, torch::Tensor nodes,
+                       torch::Tensor X, torch::Tensor Y, torch::Tensor layout,
+                       int64_t n_layers, torch::Tensor eval_counts)
+{
+    EvalMlpShape g = eval_mlp_check(params, nodes, X, Y, layout, n_layers,
+                                    eval_counts);
+    bool per_node = g.per_node;
+    int64_t D = g.D, d_in = g.d_in, act_total = g.act_total, n_eval = g.n_eval;
     int R = nodes.size(0);
     auto out = torch::empty({R, 5}, params.options());
     if (R == 0) return out;
@@ -4752,6 +5050,109 @@ torch::Tensor eval_mlp(torch::Tensor params, torch::Tensor nodes,
     size_t smem = eval_mlp_fixed_smem(D, n_eval) - 16 +
                   sizeof(float) * (size_t)tile * (d_in + act_total);
     launch_kernel(eval_mlp_kernel, R, 256, smem, current_stream(), p);
+    return out;
+}
+
+// Row stride of eval_mlp_wide_kernel's activation buffers: the widest hidden
+// layer rounded up to 8, plus 4 (4 x an odd number, see the kernel's bank
+// arithmetic); 0 for a model without hidden layers.
+static int64_t eval_mlp_wide_stride(int64_t max_hidden)
+{
+    return max_hidden > 0 ? ((max_hidden + 7) & ~(int64_t)7) + 4 : 0;
+}
+
+static size_t eval_mlp_wide_smem(int64_t rb, int64_t max_hidden)
+{
+    return sizeof(float) * (size_t)(2 * EMW_CG * EMW_LS + 2 * rb * EMW_LS +
+                                    2 * rb * eval_mlp_wide_stride(max_hidden));
+}
+
+// Rows of a block of eval_mlp_wide_kernel: the largest of 64, 32 and 16
+// whose staging tiles and two activation buffers fit the 160 KB LDS budget.
+// 0 = the old paths serve the shape: not even 16 rows fit, n_eval > 2048
+// (the pair count of the metrics epilogue) or k > EVAL_KMAX.
+static int64_t eval_mlp_wide_rb(int64_t max_hidden, int64_t k, int64_t n_eval)
+{
+    if (n_eval < 1 || n_eval > 2048 || k < 1 || k > EVAL_KMAX) return 0;
+    for (int64_t rb : {64, 32, 16})
+        if (eval_mlp_wide_smem(rb, max_hidden) <= 160 * 1024) return rb;
+    return 0;
+}
+
+static bool eval_mlp_wide_fits(std::vector<int64_t> dims, int64_t n_eval)
+{
+    if (dims.size() < 2) return false;
+    int64_t max_hidden = 0;
+    for (size_t i = 1; i + 1 < dims.size(); ++i)
+        max_hidden = std::max(max_hidden, dims[i]);
+    return eval_mlp_wide_rb(max_hidden, dims.back(), n_eval) > 0;
+}
+
+template <bool VEC>
+static void (*eval_mlp_wide_pick(int64_t rb))(EvalMlpWideArgs)
+{
+    return rb == 64   ? eval_mlp_wide_kernel<64, VEC>
+           : rb == 32 ? eval_mlp_wide_kernel<32, VEC>
+                      : eval_mlp_wide_kernel<16, VEC>;
+}
+
+// eval_mlp for the shapes past its LDS budget (and any other that
+// eval_mlp_wide_fits takes): eval_mlp_wide_kernel writes the head logits to
+// a workspace, eval_metrics_kernel in scores mode turns them into the
+// [R, 5] rows (-2 rows for empty shards).
+torch::Tensor eval_mlp_wide(torch::Tensor params, torch::Tensor nodes,
+                            torch::Tensor X, torch::Tensor Y,
+                            torch::Tensor layout, int64_t n_layers,
+                            torch::Tensor eval_counts)
+{
+    EvalMlpShape g = eval_mlp_check(params, nodes, X, Y, layout, n_layers,
+                                    eval_counts);
+    int64_t R = nodes.size(0), S = g.n_eval;
+    auto out = torch::empty({R, 5}, params.options());
+    if (R == 0) return out;
+    int64_t rb = eval_mlp_wide_rb(g.max_hidden, g.k, S);
+    TORCH_CHECK(rb > 0, "eval_mlp_wide: shape does not fit (widest hidden"
+                " layer ", g.max_hidden, ", n_eval=", S, ")");
+    if (g.per_node) {
+        // the kernels index X, Y and eval_counts by the local row id
+        TORCH_CHECK(X.size(0) == params.size(0),
+                    "per-node mode: X must hold one shard per params row");
+    }
+    auto Z = torch::empty({R, S, g.k}, params.options());
+    EvalMlpWideArgs p{};
+    p.params = params.data_ptr<float>();
+    p.X = X.data_ptr<float>();
+    p.layout = layout.data_ptr<int>();
+    p.eval_counts = g.per_node ? eval_counts.data_ptr<int>() : nullptr;
+    p.n_layers = n_layers; p.D = g.D; p.d_in = g.d_in; p.S = S; p.k = g.k;
+    p.act_stride = eval_mlp_wide_stride(g.max_hidden);
+    p.w_aligned = (uintptr_t)p.params % 16 == 0;
+    bool vec = g.d_in % 4 == 0 && (uintptr_t)p.X % 16 == 0;
+    auto kernel = vec ? eval_mlp_wide_pick<true>(rb)
+                      : eval_mlp_wide_pick<false>(rb);
+    size_t smem = eval_mlp_wide_smem(rb, g.max_hidden);
+    const int* nodes_d = nodes.data_ptr<int>();
+    // a grid's y extent ends at 65535
+    for (int64_t r0 = 0; r0 < R; r0 += 65535) {
+        p.nodes = nodes_d + r0;
+        p.Z = Z.data_ptr<float>() + r0 * S * g.k;
+        dim3 grid((unsigned)((S + rb - 1) / rb),
+                  (unsigned)std::min<int64_t>(65535, R - r0));
+        launch_kernel(kernel, grid, EMW_THREADS, smem, current_stream(), p);
+    }
+    EvalArgs a{};
+    a.nodes = nodes_d;
+    a.Y = Y.data_ptr<float>();
+    a.out = out.data_ptr<float>();
+    a.k = g.k; a.n_eval = S;
+    a.tile = 1;
+    a.eval_counts = p.eval_counts;
+    a.scores = Z.data_ptr<float>();
+    size_t ev_smem = sizeof(float) * 2 * (size_t)S
+        + ((S + 15) & ~15) * sizeof(char)
+        + sizeof(int) * EVAL_KMAX * EVAL_KMAX;
+    launch_kernel(eval_metrics_kernel, (int)R, 256, ev_smem, current_stream(),
+                  a);
     return out;
 }
 
@@ -5438,6 +5839,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("eval_mlp_tile", &eval_mlp_tile,
           "rows eval_mlp forwards per chunk for (D, d_in, act_total, n_eval);"
           " 0 when the shape does not fit");
+    m.def("eval_mlp_wide", &eval_mlp_wide,
+          "eval_mlp past its LDS budget: row-blocked MFMA forward to a logits"
+          " workspace + the metrics epilogue, same arguments and result");
+    m.def("eval_mlp_wide_fits", &eval_mlp_wide_fits,
+          "whether eval_mlp_wide takes an MLP of (dims, n_eval)");
     m.def("tick_kmeans", &tick_kmeans,
           "fused centroid merge + assign/EMA k-means tick (K11)");
 }
