@@ -10,6 +10,13 @@ Synthetic MNIST-shaped data (784 features, 10 classes).
 ``--batch-size`` sets the minibatch (31 still fits the LDS kernels),
 ``--mode`` the CreateModelMode. The script prints the tick path the
 configuration gets and the last global evaluation.
+
+``--pens`` runs PENS neighbour selection (``BatchedPENSGossipSimulator``) on
+the same data with minibatches of 64 unless ``--batch-size`` says otherwise:
+from there on the step-1 event misses the LDS plan of ``tick_pens_kernel``
+(``4 * (D + rows * 784 + rows * 10)`` bytes; 32 rows still fit) and runs
+``tick_pens_wide_kernel``, which scores all candidates in one MFMA GEMM. The
+script then prints the PENS event path as well.
 """
 
 import os
@@ -26,6 +33,7 @@ from gossipy_amd.core import AntiEntropyProtocol, CreateModelMode
 from gossipy_amd.data import make_synthetic_classification
 from gossipy_amd.engine import (
     BatchedGossipSimulator,
+    BatchedPENSGossipSimulator,
     DataArena,
     EngineConfig,
     LogRegSpec,
@@ -39,9 +47,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nodes", type=int, default=100)
     ap.add_argument("--rounds", type=int, default=20)
-    ap.add_argument("--batch-size", type=int, default=32)
+    ap.add_argument("--batch-size", type=int, default=None,
+                    help="default 32, or 64 with --pens")
     ap.add_argument("--mode", choices=sorted(MODES), default="merge_update")
+    ap.add_argument("--pens", action="store_true",
+                    help="PENS neighbour selection (MERGE_UPDATE only)")
     args = ap.parse_args()
+    if args.batch_size is None:
+        args.batch_size = 64 if args.pens else 32
 
     device = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
     n, d, k = args.nodes, 784, 10
@@ -65,12 +78,19 @@ def main():
         sampling_eval=0.1,
         seed=42,
     )
-    sim = BatchedGossipSimulator(cfg, spec, data, device=device)
-    if sim.backend.name == "hip":
-        path = sim.backend.logreg_tick_path(spec, data)
+    if args.pens:
+        sim = BatchedPENSGossipSimulator(
+            cfg, spec, data, n_sampled=4, m_top=2,
+            step1_rounds=max(1, args.rounds // 2), device=device,
+        )
     else:
-        path = "torch (no GPU)"
+        sim = BatchedGossipSimulator(cfg, spec, data, device=device)
+    hip = sim.backend.name == "hip"
+    path = sim.backend.logreg_tick_path(spec, data) if hip else "torch (no GPU)"
     print(f"logreg {d}x{k}, batch {args.batch_size}: tick path {path}")
+    if args.pens:
+        path = sim.backend.pens_tick_path(spec, data) if hip else "torch (no GPU)"
+        print(f"pens_tick_path {path}")
     report = SimulationReport()
     sim.add_receiver(report)
     sim.init_nodes()

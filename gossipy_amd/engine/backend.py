@@ -1896,13 +1896,30 @@ class HIPBackend(TorchBackend):
         streamed from the arena through MFMA tiles). ``GOSSIPY_LOGREG_WIDE=1``
         forces ``"wide"``; with ``=0`` a shape past the budget raises the
         budget error instead, as does a shape whose model row alone misses
-        the LDS. Partitioned, sampled and PENS logreg ticks have the LDS
-        kernels only."""
+        the LDS. Partitioned and sampled logreg ticks have the LDS kernels
+        only; the PENS event has a split of its own, see
+        ``pens_tick_path``."""
         if spec.family != "logreg" or spec.n_parts > 0 or spec.sample_size > 0:
             raise ValueError("logreg_tick_path: a plain LogRegSpec is required")
         return self.ext.logreg_tick_path(
             spec.d_in, spec.n_classes, spec.batch_size, data.x.shape[1],
             _MODE_ID[spec.mode],
+        )
+
+    def pens_tick_path(self, spec, data) -> str:
+        """Which kernel a PENS step-1 event of the plain logreg ``spec`` runs
+        on the shards of ``data``: ``"lds"`` (``tick_pens_kernel``: one model
+        slab, the staged minibatch and its dz block, ``4 * (D + rows * d_in +
+        rows * n_classes)`` bytes, in one workgroup's 160 KB of LDS) whenever
+        that fits, else ``"wide"`` (``tick_pens_wide_kernel``: all candidates
+        scored in one MFMA GEMM over the streamed shard, then the wide tick's
+        update). ``GOSSIPY_LOGREG_WIDE=1`` forces ``"wide"``; with ``=0`` a
+        shape past the budget raises the budget error instead. A model row
+        that misses the LDS alone (4096x16) raises in every setting."""
+        if spec.family != "logreg" or spec.n_parts > 0 or spec.sample_size > 0:
+            raise ValueError("pens_tick_path: a plain LogRegSpec is required")
+        return self.ext.pens_tick_path(
+            spec.d_in, spec.n_classes, spec.batch_size, data.x.shape[1],
         )
 
     def _family_call(self, spec, dev):

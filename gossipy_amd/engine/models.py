@@ -183,9 +183,13 @@ class LogRegSpec(_PartitionMixin):
     one model row and the ``rows * n_classes`` dz block in LDS and streams
     the minibatch through MFMA tiles. ``HIPBackend.logreg_tick_path`` tells
     which, and ``GOSSIPY_LOGREG_WIDE=1`` / ``=0`` force / forbid the wide one.
+    The PENS step-1 event follows the same split on its own plan of
+    ``4 * (D + rows * d_in + rows * n_classes)`` bytes: past it
+    ``tick_pens_wide_kernel`` scores all candidates in one MFMA GEMM over the
+    streamed shard (``HIPBackend.pens_tick_path``, the same knob).
     Still bound to the LDS budget: a model row that misses it alone (4096x16),
-    ``n_parts``, ``sample_size``, the PENS event and the opt-in cooperative
-    round, which raise a budget error past it.
+    ``n_parts``, ``sample_size`` and the opt-in cooperative round, which
+    raise a budget error past it.
     """
 
     d_in: int

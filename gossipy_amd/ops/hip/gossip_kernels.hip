@@ -56,6 +56,10 @@
 //                           batch streamed through double-buffered tiles,
 //                           forward and weight gradient on MFMA; picked
 //                           host-side, see logreg_use_wide.
+//   tick_pens_wide_kernel — the logreg PENS event past the LDS budget: all
+//                           candidates scored in one MFMA GEMM that streams
+//                           the shard once per 16 candidates, then the merge
+//                           and the wide tick's update; see pens_use_wide.
 //   eval_metrics_kernel   — K13: accuracy / macro P-R-F1 / pairwise AUC of
 //                           R affine or margin models (or precomputed
 //                           scores) on a shared set or per-node shards.
@@ -2571,6 +2575,8 @@ struct PensArgs {
     int d, k, Smax, D, m_top, n_total;
     float lr, wd;
     int epochs, bs;
+    // tick_pens_wide_kernel only: the update's tile geometry, as LogregArgs'
+    int wide_rb, wide_lkp;
 };
 
 // Top-min(m_top, n_cand) candidates by correct count, stable in arrival
@@ -3159,6 +3165,299 @@ __global__ LRW_FN void __launch_bounds__(LRW_THREADS)
 tick_logreg_wide_kernel(LogregArgs a)
 {
     lrw_process_node<LIM, VEC>(a, blockIdx.x);
+}
+
+// ---------------------------------------------------------------------------
+// wide PENS step-1 event: tick_pens_kernel's event for the shapes whose model
+// row, staged batch and dz block miss its LDS budget (3072x10 at any batch
+// size, 561x6 full-batch, 784x10 from batches of 64 up). One workgroup of 256
+// threads per event, two phases that share the dynamic LDS.
+//
+// Phase A, scoring: Z[rows, n_cand x 16] = X_shard · [W_c1; W_c2; ...]ᵀ on
+// v_mfma_f32_16x16x4_f32, each candidate's k <= 16 classes one zero-padded
+// column tile. The own model is not in LDS yet, so the phase has the whole
+// allocation: two staging tiles of PW_RB x PW_KP shard columns and two of
+// PW_G x 16 x PW_KP candidate weights (90 KB, never more than the wide tick's
+// shape limit allows: the launch asks for the larger of the two phases).
+//   split     Candidates, not K, go over the 4 waves: of a pass's PW_G = 16
+//             candidates wave w owns w, w + 4, w + 8, w + 12 and, for each,
+//             all PW_RT = 4 row tiles of the row block: 16 accumulators that
+//             stay in registers across the K panels of the row block. A K
+//             sum is never split, so no partials cross LDS. An event of more
+//             than PW_G candidates takes several passes over the (by then
+//             L2-resident) shard; registers do not depend on n_cand.
+//   movement  Every X panel is read once per pass for all its candidates.
+//             A thread loads 4 consecutive columns of a tile row, rows of 8
+//             threads along d: one 16-byte load where the address allows it,
+//             decided per load (a slot row starts at slot * D + j * d floats,
+//             D = k * (d + 1): rarely a multiple of 4), scalar loads
+//             otherwise; X is 16-byte loaded under VEC as in the wide tick.
+//             Panel p + 1 is loaded into registers before the MFMAs on panel
+//             p and stored to the other tiles after them; the chain runs
+//             through the row blocks of a pass without a bubble.
+//   banks     64 banks of 4 bytes. Both operands are read as 16 rows x 4
+//             consecutive columns: lane l takes X[l & 15][k0 + (l >> 4)] and
+//             W_c[l & 15][k0 + (l >> 4)], bank ((l & 15) * LS + (l >> 4)) mod
+//             64. LS = PW_KP + 4 = 36 = 4 * 9 with 9 odd: (l & 15) * 9 mod 16
+//             takes all 16 residues, so (l & 15) * LS mod 64 is the 16
+//             multiples of 4, and adding l >> 4 in 0..3 gives 64 different
+//             banks. A stride of 32 would put every other row on one bank.
+//   epilogue  On the accumulators (lane l, register q: row (l >> 4) * 4 + q,
+//             class l & 15): add the bias, arg-max over the 16 class lanes
+//             with 4 xor-shuffles (a padded class is -inf and never wins;
+//             of equal scores the lowest class wins, the strict `>` of
+//             tick_pens_kernel), compare with the label. Rows at or past the
+//             shard's count are neither read nor counted. Hits are summed in
+//             a register over the pass and added to correct[c] in LDS with an
+//             integer atomic.
+//
+// Phase B: pens_select, then tick_pens_kernel's merge in its expression
+// order on the LDS row W, then lrw_update with the wide tick's geometry.
+// ---------------------------------------------------------------------------
+
+constexpr int PW_G = 16;                  // candidates of a scoring pass
+constexpr int PW_CW = PW_G / LRW_WAVES;   // of which a wave owns
+constexpr int PW_RB = 64;                 // shard rows of a row block
+constexpr int PW_RT = PW_RB / 16;
+constexpr int PW_KP = 32;                 // columns of a K panel
+constexpr int PW_LS = PW_KP + 4;          // row stride of a staging tile
+constexpr int PW_WROWS = PW_G * 16;       // rows of a weight tile
+constexpr int PW_WNV = PW_WROWS * PW_KP / LRW_THREADS / 4;  // float4 / thread
+constexpr int PW_XNV = PW_RB * PW_KP / LRW_THREADS / 4;
+constexpr size_t PW_SCORE_BYTES =
+    sizeof(float) * 2 * (PW_WROWS + PW_RB) * PW_LS;
+
+struct PwPanel {
+    float4 w[PW_WNV], x[PW_XNV];
+};
+
+// columns c .. c + 3 of a row of n floats, zeros from column n on; `vec`
+// allows the 16-byte load where the address is aligned and all 4 exist
+DEV_INLINE LRW_FN float4 pw_load4(const float* row, int c, int n, bool vec)
+{
+    const float* p = row + c;
+    if (vec && c + 4 <= n && ((uintptr_t)p & 15) == 0)
+        return *reinterpret_cast<const float4*>(p);
+    return make_float4(c < n ? p[0] : 0.f, c + 1 < n ? p[1] : 0.f,
+                       c + 2 < n ? p[2] : 0.f, c + 3 < n ? p[3] : 0.f);
+}
+
+// Registers <- panel col0.. of the pass's weight rows (wrow[u]: the thread's
+// row of tile rows 32 u + tid / 8, or null: padding, not read) and of shard
+// rows row0.. (zeros, and no read, from row m and column d on)
+template <bool VEC>
+DEV_INLINE LRW_FN void pw_load(PwPanel& t, const float* (&wrow)[PW_WNV],
+                               const float* Xn, int m, int d, int row0,
+                               int col0)
+{
+    const int tid = threadIdx.x, c = col0 + ((tid & 7) << 2);
+#pragma unroll
+    for (int u = 0; u < PW_WNV; ++u) {
+        t.w[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (wrow[u] && c < d) t.w[u] = pw_load4(wrow[u], c, d, true);
+    }
+#pragma unroll
+    for (int u = 0; u < PW_XNV; ++u) {
+        int r = row0 + (tid >> 3) + u * 32;
+        t.x[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (r < m && c < d) t.x[u] = pw_load4(Xn + (long)r * d, c, d, VEC);
+    }
+}
+
+// the staging tiles wt, xt (row stride PW_LS) <- registers
+DEV_INLINE LRW_FN void pw_store(const PwPanel& t, float* wt, float* xt)
+{
+    const int o = (threadIdx.x >> 3) * PW_LS + ((threadIdx.x & 7) << 2);
+#pragma unroll
+    for (int u = 0; u < PW_WNV; ++u)
+        *reinterpret_cast<float4*>(wt + o + u * 32 * PW_LS) = t.w[u];
+#pragma unroll
+    for (int u = 0; u < PW_XNV; ++u)
+        *reinterpret_cast<float4*>(xt + o + u * 32 * PW_LS) = t.x[u];
+}
+
+// correct[c] += rows of the m-row shard (Xn, Yn) whose label candidate c of
+// cand[0 .. n_cand) predicts; m, n_cand > 0. `tiles` is PW_SCORE_BYTES.
+template <bool VEC>
+DEV_INLINE LRW_FN void pw_score(const PensArgs& a, const float* Xn,
+                                const float* Yn, int m, const int* cand,
+                                int n_cand, float* tiles, int* correct)
+{
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+    const int li = lane & 15, lq = lane >> 4;
+    float* wst = tiles;                      // 2 x PW_WROWS x PW_LS
+    float* xst = wst + 2 * PW_WROWS * PW_LS;  // 2 x PW_RB x PW_LS
+    const int nP = (a.d + PW_KP - 1) / PW_KP;
+    const int T = ((m + PW_RB - 1) / PW_RB) * nP;
+    for (int c0 = 0; c0 < n_cand; c0 += PW_G) {
+        const int ncp = min(PW_G, n_cand - c0);  // candidates of the pass
+        // loads: the thread's tile rows are class (tid / 8) % 16 of the
+        // candidates tid / 128 + 2 u
+        const float* wrow[PW_WNV];
+#pragma unroll
+        for (int u = 0; u < PW_WNV; ++u) {
+            int tc = (tid >> 7) + 2 * u, j = (tid >> 3) & 15;
+            wrow[u] = (j < a.k && tc < ncp)
+                ? a.slots + (long)cand[c0 + tc] * a.D + j * a.d : nullptr;
+        }
+        // MFMAs: candidates wave + 4 j, the lane's class li of each
+        float bias[PW_CW];
+        int hits[PW_CW];
+        f32x4_t acc[PW_RT][PW_CW];
+#pragma unroll
+        for (int j = 0; j < PW_CW; ++j) {
+            int tc = wave + j * LRW_WAVES;
+            bias[j] = (li < a.k && tc < ncp)
+                ? a.slots[(long)cand[c0 + tc] * a.D + a.k * a.d + li] : 0.f;
+            hits[j] = 0;
+#pragma unroll
+            for (int r = 0; r < PW_RT; ++r)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) acc[r][j][q] = 0.f;
+        }
+        PwPanel t;
+        pw_load<VEC>(t, wrow, Xn, m, a.d, 0, 0);
+        pw_store(t, wst, xst);
+        __syncthreads();
+        for (int i = 0; i < T; ++i) {
+            const int rb = i / nP, p = i - rb * nP;
+            if (i + 1 < T) {
+                int rb1 = (i + 1) / nP, p1 = (i + 1) - rb1 * nP;
+                pw_load<VEC>(t, wrow, Xn, m, a.d, rb1 * PW_RB, p1 * PW_KP);
+            }
+            const float* wt = wst + (i & 1) * PW_WROWS * PW_LS + li * PW_LS + lq;
+            const float* xt = xst + (i & 1) * PW_RB * PW_LS + li * PW_LS + lq;
+            const int kleft = a.d - p * PW_KP;  // live columns: zeros past them
+            const int kend = min(PW_KP, (kleft + 3) & ~3);
+            // row tiles of the block that hold a row below m
+            const int nrt = (min(PW_RB, m - rb * PW_RB) + 15) >> 4;
+            for (int kk = 0; kk < kend; kk += 4) {
+                float bv[PW_CW];
+#pragma unroll
+                for (int j = 0; j < PW_CW; ++j)
+                    bv[j] = wt[(wave + j * LRW_WAVES) * 16 * PW_LS + kk];
+#pragma unroll
+                for (int r = 0; r < PW_RT; ++r) {
+                    if (r < nrt) {
+                        float av = xt[r * 16 * PW_LS + kk];
+#pragma unroll
+                        for (int j = 0; j < PW_CW; ++j)
+                            if (wave + j * LRW_WAVES < ncp)
+                                acc[r][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                                    av, bv[j], acc[r][j], 0, 0, 0);
+                    }
+                }
+            }
+            if (p == nP - 1) {  // the row block is done: count its hits
+#pragma unroll
+                for (int r = 0; r < PW_RT; ++r) {
+                    if (r < nrt) {
+                        int y[4];
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) {
+                            int s = rb * PW_RB + r * 16 + lq * 4 + q;
+                            y[q] = s < m ? (int)Yn[s] : -1;  // -1: no class
+                        }
+#pragma unroll
+                        for (int j = 0; j < PW_CW; ++j) {
+                            if (wave + j * LRW_WAVES < ncp) {
+#pragma unroll
+                                for (int q = 0; q < 4; ++q) {
+                                    float v = li < a.k ? acc[r][j][q] + bias[j]
+                                                       : -INFINITY;
+                                    int bj = li;
+#pragma unroll
+                                    for (int off = 8; off > 0; off >>= 1) {
+                                        float ov = __shfl_xor(v, off, WAVE);
+                                        int oj = __shfl_xor(bj, off, WAVE);
+                                        if (ov > v || (ov == v && oj < bj)) {
+                                            v = ov;
+                                            bj = oj;
+                                        }
+                                    }
+                                    if (li == 0 && bj == y[q]) hits[j] += 1;
+                                }
+                            }
+                        }
+                    }
+#pragma unroll
+                    for (int j = 0; j < PW_CW; ++j)
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) acc[r][j][q] = 0.f;
+                }
+            }
+            if (i + 1 < T)
+                pw_store(t, wst + ((i + 1) & 1) * PW_WROWS * PW_LS,
+                         xst + ((i + 1) & 1) * PW_RB * PW_LS);
+            __syncthreads();
+        }
+        // a candidate has one wave: its 4 lanes with li == 0 hold the counts.
+        // The next pass's first store lands on tile 0, which every wave left
+        // at the loop's last barrier.
+#pragma unroll
+        for (int j = 0; j < PW_CW; ++j)
+            if (hits[j]) atomicAdd(&correct[c0 + wave + j * LRW_WAVES], hits[j]);
+    }
+}
+
+template <bool VEC>
+__global__ LRW_FN void __launch_bounds__(LRW_THREADS)
+tick_pens_wide_kernel(PensArgs a)
+{
+    const int i = blockIdx.x, node = a.nodes[i], tid = threadIdx.x;
+    const int lo = a.ptr[i], n_cand = a.ptr[i + 1] - lo;
+    extern __shared__ float4 lrw_sm[];
+    __shared__ int correct[PENS_MAX_CAND];
+    __shared__ int sel[PENS_MAX_CAND];
+    const int c_n = a.dcounts[node];
+    const float* Xn = a.X + (long)node * a.Smax * a.d;
+    const float* Yn = a.Y + (long)node * a.Smax;
+
+    // --- phase A: score the candidates, the tiles over the whole allocation
+    for (int c = tid; c < n_cand; c += LRW_THREADS) correct[c] = 0;
+    __syncthreads();
+    if (c_n > 0 && n_cand > 0)
+        pw_score<VEC>(a, Xn, Yn, c_n, a.cslots + lo, n_cand,
+                      reinterpret_cast<float*>(lrw_sm), correct);
+    __syncthreads();
+    if (tid == 0)
+        pens_select(correct, sel, n_cand, a.m_top,
+                    a.counts + (long)node * a.n_total, a.cowners + lo);
+    __syncthreads();
+
+    // --- phase B: W[D], the dz block and the update's tiles, as in
+    // lrw_process_node; merge (own + sum selected) / (m+1), age = max
+    float* W = reinterpret_cast<float*>(lrw_sm);
+    const int bsmax = (a.bs == 0) ? a.Smax : min(a.bs, a.Smax);
+    float* zb = W + ((a.D + 3) & ~3);
+    float* stage = zb + ((bsmax * a.k + 3) & ~3);
+    float* prow = a.params + (long)node * a.D;
+    copy_row(W, prow, a.D);
+    __syncthreads();
+    int n_sel = 0;
+    int age = a.ages[node];
+    for (int c = 0; c < n_cand; ++c) {
+        if (!sel[c]) continue;
+        n_sel += 1;
+        const int slot = a.cslots[lo + c];
+        const float* Wc = a.slots + (long)slot * a.D;
+        for (int e = tid; e < a.D; e += LRW_THREADS) W[e] += Wc[e];
+        age = max(age, a.slot_ages[slot]);
+    }
+    float inv = 1.0f / (n_sel + 1);
+    for (int e = tid; e < a.D; e += LRW_THREADS) W[e] *= inv;
+    __syncthreads();
+
+    // --- local update
+    LogregArgs u{};
+    u.X = a.X; u.Y = a.Y; u.counts = a.dcounts;
+    u.d = a.d; u.k = a.k; u.Smax = a.Smax; u.D = a.D;
+    u.lr = a.lr; u.wd = a.wd; u.epochs = a.epochs; u.bs = a.bs;
+    u.wide_rb = a.wide_rb; u.wide_lkp = a.wide_lkp;
+    lrw_update<VEC>(u, node, c_n, W, zb, stage, age);
+    __syncthreads();
+    copy_row(prow, W, a.D);
+    if (tid == 0) a.ages[node] = age;
 }
 
 // ---------------------------------------------------------------------------
@@ -3857,10 +4156,15 @@ static size_t logreg_lds_bytes(int64_t d, int64_t k, int64_t rows)
 // batch-streaming tick_logreg_wide_kernel. GOSSIPY_LOGREG_WIDE=1 forces the
 // wide kernel on any shape (tests, A/B runs), =0 turns it off, which restores
 // the budget error.
-static bool logreg_use_wide(size_t lds_bytes)
+static int logreg_wide_knob()  // 1, 0, or -1 when unset
 {
     const char* v = getenv("GOSSIPY_LOGREG_WIDE");
-    int knob = (v && *v) ? (atoi(v) != 0) : -1;
+    return (v && *v) ? (atoi(v) != 0) : -1;
+}
+
+static bool logreg_use_wide(size_t lds_bytes)
+{
+    int knob = logreg_wide_knob();
     if (knob == 1) return true;
     bool fits = lds_bytes <= 160 * 1024;
     TORCH_CHECK(fits || knob != 0, "logreg LDS budget exceeded: ", lds_bytes);
@@ -3878,7 +4182,8 @@ struct LogregWideGeom {
     size_t smem;
 };
 
-static LogregWideGeom logreg_wide_geom(int64_t d, int64_t k, int64_t rows)
+static LogregWideGeom logreg_wide_geom(int64_t d, int64_t k, int64_t rows,
+                                       size_t budget = 160 * 1024)
 {
     rows = std::max<int64_t>(rows, 1);
     size_t D = (size_t)(k * d + k);
@@ -3892,11 +4197,11 @@ static LogregWideGeom logreg_wide_geom(int64_t d, int64_t k, int64_t rows)
     auto tiles = [&] {
         return sizeof(float) * 2 * g.RB * ((size_t)(1 << g.lkp) + LRW_PAD);
     };
-    while (fixed + tiles() > 160 * 1024 && (g.lkp > 5 || g.RB > 16)) {
+    while (fixed + tiles() > budget && (g.lkp > 5 || g.RB > 16)) {
         if (g.lkp > 5) g.lkp -= 1; else g.RB /= 2;
     }
     g.smem = fixed + tiles();
-    TORCH_CHECK(g.smem <= 160 * 1024,
+    TORCH_CHECK(g.smem <= budget,
         "logreg LDS budget exceeded (", g.smem, " B): the wide kernel keeps one"
         " model row and one dz block in LDS (", D, " + ", rows * k,
         " floats here) next to two staging tiles; shrink d_in, n_classes or"
@@ -3916,6 +4221,55 @@ static std::string logreg_tick_path(int64_t d, int64_t k, int64_t bs,
     if (!logreg_use_wide(logreg_lds_bytes(d, k, rows))) return "lds";
     logreg_wide_geom(d, k, rows);  // raises when even the floor misses
     return "wide";
+}
+
+// bytes of dynamic LDS tick_pens_kernel needs: one model slab, the staged
+// batch of `rows` rows and its dz block
+static size_t pens_lds_bytes(int64_t d, int64_t k, int64_t rows)
+{
+    size_t D = (size_t)(k * d + k);
+    return sizeof(float) * (D + (size_t)rows * d + (size_t)rows * k);
+}
+
+// Dynamic LDS of tick_pens_wide_kernel: the larger of its two phases. Phase B
+// is the wide tick's geometry, planned under the 160 KB less the kernel's
+// static correct[] / sel[]; phase A's tiles are fixed (PW_SCORE_BYTES), far
+// below that, so the shape limit is the geometry's.
+static LogregWideGeom pens_wide_geom(int64_t d, int64_t k, int64_t rows)
+{
+    LogregWideGeom g = logreg_wide_geom(
+        d, k, rows, 160 * 1024 - 2 * sizeof(int) * PENS_MAX_CAND);
+    g.smem = std::max(g.smem, PW_SCORE_BYTES);
+    return g;
+}
+
+// Which kernel serves a logreg PENS event, mirroring logreg_use_wide:
+// tick_pens_kernel whenever its `lds_bytes` fit, else tick_pens_wide_kernel
+// with the geometry written to *g. GOSSIPY_LOGREG_WIDE=1 forces the wide
+// kernel, =0 restores the budget error. A model row that misses even the wide
+// geometry raises that geometry's message in every setting.
+static bool pens_use_wide(size_t lds_bytes, int64_t d, int64_t k, int64_t rows,
+                          LogregWideGeom* g)
+{
+    int knob = logreg_wide_knob();
+    bool fits = lds_bytes <= 160 * 1024;
+    if (fits && knob != 1) return false;
+    *g = pens_wide_geom(d, k, rows);
+    TORCH_CHECK(fits || knob != 0, "pens LDS budget exceeded: ", lds_bytes,
+                " (GOSSIPY_LOGREG_WIDE=0 keeps tick_pens_wide_kernel off)");
+    return true;
+}
+
+// "lds" or "wide": the kernel tick_pens runs for a logreg PENS event on
+// shards of stride Smax
+static std::string pens_tick_path(int64_t d, int64_t k, int64_t bs,
+                                  int64_t Smax)
+{
+    TORCH_CHECK(k <= KMAX, "n_classes > ", KMAX, " unsupported");
+    int rows = batch_rows(bs, (int)Smax);
+    LogregWideGeom g;
+    return pens_use_wide(pens_lds_bytes(d, k, rows), d, k, rows, &g) ? "wide"
+                                                                     : "lds";
 }
 
 static Plan<LogregArgs> logreg_plan(
@@ -4006,7 +4360,8 @@ static Plan<LogregPartArgs> logreg_part_plan(
                            (size_t)bsmax * a.k) +
               sizeof(int) * 2 * a.P;
     TORCH_CHECK(L.smem <= 160 * 1024, "partitioned logreg LDS budget exceeded: ",
-                L.smem, " (the wide kernel covers the plain logreg tick only)");
+                L.smem, " (the wide kernels cover the plain logreg tick and the"
+                " PENS event only)");
     L.kernel = tick_logreg_part_kernel;
     L.threads = 128;
     L.snap = {a.D, a.D, 0, a.P};
@@ -4028,7 +4383,8 @@ static Plan<LogregSampArgs> logreg_samp_plan(
     L.smem = sizeof(float) * (3 * a.D + (size_t)bsmax * a.d +
                               (size_t)bsmax * a.k);
     TORCH_CHECK(L.smem <= 160 * 1024, "sampled logreg LDS budget exceeded: ",
-                L.smem, " (the wide kernel covers the plain logreg tick only)");
+                L.smem, " (the wide kernels cover the plain logreg tick and the"
+                " PENS event only)");
     L.kernel = big_batch(bs, a.Smax) ? tick_logreg_samp_kernel<true>
                                      : tick_logreg_samp_kernel<false>;
     L.threads = LOGREG_THREADS;
@@ -4803,7 +5159,7 @@ void tick_pens(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
     TORCH_CHECK(k <= KMAX, "n_classes > ", KMAX, " unsupported");
     int n = nodes.size(0);
     if (n == 0) return;
-    PensArgs a;
+    PensArgs a{};
     a.params = params.data_ptr<float>(); a.ages = ages.data_ptr<int>();
     a.slots = slots.data_ptr<float>(); a.slot_ages = slot_ages.data_ptr<int>();
     a.nodes = nodes.data_ptr<int>(); a.ptr = ptr.data_ptr<int>();
@@ -4814,11 +5170,18 @@ void tick_pens(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
     a.d = d; a.k = k; a.Smax = X.size(1); a.D = params.size(1);
     a.m_top = m_top; a.n_total = counts.size(1);
     a.lr = lr; a.wd = wd; a.epochs = epochs; a.bs = bs;
-    int bsmax = (bs == 0) ? a.Smax : std::min<int>(bs, a.Smax);
-    size_t smem = sizeof(float) * (a.D + (size_t)bsmax * a.d +
-                                   (size_t)bsmax * a.k);
-    TORCH_CHECK(smem <= 160 * 1024, "pens LDS budget exceeded: ", smem,
-                " (the wide kernel covers the plain logreg tick only)");
+    int bsmax = batch_rows(bs, a.Smax);
+    size_t smem = pens_lds_bytes(d, k, bsmax);
+    LogregWideGeom g;
+    if (pens_use_wide(smem, d, k, bsmax, &g)) {
+        a.wide_rb = g.RB; a.wide_lkp = g.lkp;
+        // 16-byte loads need every shard row to start on such a boundary
+        bool vec = d % 4 == 0 && (uintptr_t)a.X % 16 == 0;
+        launch_kernel(vec ? tick_pens_wide_kernel<true>
+                          : tick_pens_wide_kernel<false>,
+                      n, LRW_THREADS, g.smem, current_stream(), a);
+        return;
+    }
     hipLaunchKernelGGL(big_batch(bs, a.Smax) ? tick_pens_kernel<true>
                                              : tick_pens_kernel<false>,
                        dim3(n), dim3(LOGREG_THREADS), smem, current_stream(),
@@ -5780,6 +6143,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("logreg_tick_path", &logreg_tick_path,
           "\"lds\" or \"wide\": the kernel of a plain logreg tick (d, k, bs,"
           " Smax, mode); host code, no GPU needed");
+    m.def("pens_tick_path", &pens_tick_path,
+          "\"lds\" or \"wide\": the kernel of a logreg PENS event (d, k, bs,"
+          " Smax); host code, no GPU needed");
     m.def("mlp_tick_path", &mlp_tick_path,
           "\"lds\" or \"wide\": the kernel tick_mlp / run_round_mlp run for"
           " (dims, batch_size, Smax, mode)");
