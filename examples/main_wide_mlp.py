@@ -12,6 +12,14 @@ split: past the budget every evaluated node's own test split is forwarded by
 ``eval_mlp_wide_kernel`` (a row-blocked MFMA forward that streams the
 weights through LDS) in place of a per-node Python loop.
 
+``--pens`` runs PENS neighbour selection (``BatchedPENSGossipSimulator``) on
+the same data. The LDS kernel of the step-1 event cannot hold a 784-100-10
+row, so the script selects the wide route (``GOSSIPY_PENS_MLP_WIDE=1``
+unless the variable is already set): ``pens_mlp_score_kernel`` forwards every
+candidate of every event over a (row block, candidate) grid, and
+``tick_pens_mlp_wide_kernel`` selects, merges and updates. The script then
+prints the PENS event path as well.
+
 ``--hidden`` sets the hidden widths, ``--mode`` the CreateModelMode,
 ``--test-shards`` gives every node a test split of its own in place of the
 shared set. The script prints the tick path the configuration gets and the
@@ -32,6 +40,7 @@ from gossipy_amd.core import AntiEntropyProtocol, CreateModelMode
 from gossipy_amd.data import make_synthetic_classification
 from gossipy_amd.engine import (
     BatchedGossipSimulator,
+    BatchedPENSGossipSimulator,
     DataArena,
     EngineConfig,
     MLPSpec,
@@ -55,7 +64,12 @@ def main():
         help="evaluate every node on a test split of its own (a tenth of"
              " its rows) instead of one shared set",
     )
+    ap.add_argument("--pens", action="store_true",
+                    help="PENS neighbour selection (MERGE_UPDATE only), on"
+                         " the wide route of the step-1 event")
     args = ap.parse_args()
+    if args.pens:
+        os.environ.setdefault("GOSSIPY_PENS_MLP_WIDE", "1")
 
     device = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
     n, d, k = args.nodes, 784, 10
@@ -86,12 +100,19 @@ def main():
         sampling_eval=0.1,
         seed=42,
     )
-    sim = BatchedGossipSimulator(cfg, spec, data, device=device)
-    if sim.backend.name == "hip":
-        path = sim.backend.mlp_tick_path(spec, data)
+    if args.pens:
+        sim = BatchedPENSGossipSimulator(
+            cfg, spec, data, n_sampled=4, m_top=2,
+            step1_rounds=max(1, args.rounds // 2), device=device,
+        )
     else:
-        path = "torch (no GPU)"
+        sim = BatchedGossipSimulator(cfg, spec, data, device=device)
+    hip = sim.backend.name == "hip"
+    path = sim.backend.mlp_tick_path(spec, data) if hip else "torch (no GPU)"
     print(f"MLP {'-'.join(map(str, spec.dims))}, D = {spec.D}: tick path {path}")
+    if args.pens:
+        path = sim.backend.pens_tick_path(spec, data) if hip else "torch (no GPU)"
+        print(f"pens_tick_path {path}")
     report = SimulationReport()
     sim.add_receiver(report)
     sim.init_nodes()

@@ -1498,6 +1498,20 @@ class HIPBackend(TorchBackend):
                 f" score at most {max_cand} per event (lower n_sampled)"
             )
         dev = state.params.device
+        cand = (
+            pens_slots.to(dev, torch.int32),
+            pens_owners.to(dev, torch.int32),
+        )
+        if spec.family == "mlp":
+            # the event of each candidate, for the wide route's scorer (one
+            # block per row block and candidate); built on the host from
+            # pens_ptr, so it costs no sync either
+            lens = pens_ptr.diff()
+            cand += (
+                torch.repeat_interleave(
+                    torch.arange(len(lens)), lens
+                ).to(dev, torch.int32),
+            )
         events = (
             state.params,
             state.ages,
@@ -1505,8 +1519,7 @@ class HIPBackend(TorchBackend):
             pool.slot_ages,
             pens_nodes.to(dev, torch.int32),
             pens_ptr.to(dev, torch.int32),
-            pens_slots.to(dev, torch.int32),
-            pens_owners.to(dev, torch.int32),
+            *cand,
             counts,
             data.x,
             data.y,
@@ -1859,8 +1872,9 @@ class HIPBackend(TorchBackend):
         fits, else ``"wide"`` (``tick_mlp_wide_kernel``: rows in device
         memory, the minibatch read from the arena). ``GOSSIPY_MLP_WIDE=1``
         forces ``"wide"``; with ``=0`` a shape past the budget raises the
-        budget error instead. Partitioned, sampled and PENS MLP ticks have
-        the LDS kernels only."""
+        budget error instead. Partitioned and sampled MLP ticks have the LDS
+        kernels only; the PENS event has a split and a knob of its own, see
+        ``pens_tick_path``."""
         if spec.family != "mlp" or spec.n_parts > 0 or spec.sample_size > 0:
             raise ValueError("mlp_tick_path: a plain MLPSpec is required")
         return self.ext.mlp_tick_path(
@@ -1915,9 +1929,30 @@ class HIPBackend(TorchBackend):
         scored in one MFMA GEMM over the streamed shard, then the wide tick's
         update). ``GOSSIPY_LOGREG_WIDE=1`` forces ``"wide"``; with ``=0`` a
         shape past the budget raises the budget error instead. A model row
-        that misses the LDS alone (4096x16) raises in every setting."""
-        if spec.family != "logreg" or spec.n_parts > 0 or spec.sample_size > 0:
-            raise ValueError("pens_tick_path: a plain LogRegSpec is required")
+        that misses the LDS alone (4096x16) raises in every setting.
+
+        For a plain ``MLPSpec``: ``"lds"`` (``tick_pens_mlp_kernel``: one
+        model slab, the staged minibatch, activations and two gradient
+        buffers in LDS; one block per receiver scores its candidates one
+        after another) or ``"wide"`` (``pens_mlp_score_kernel``: every
+        candidate of every event forwarded over a (row block, candidate)
+        grid with the weights streamed through LDS, then
+        ``tick_pens_mlp_wide_kernel``: selection, in-place merge and the
+        wide tick's update). The wide route is opt-in:
+        ``GOSSIPY_PENS_MLP_WIDE=1`` selects it on any shape; unset or ``0``
+        a shape past the budget (784-100-10) raises the budget error, which
+        names the knob. Under the knob only a hidden layer too wide for the
+        scorer's activation buffers raises."""
+        if spec.n_parts > 0 or spec.sample_size > 0 or spec.family not in (
+            "logreg", "mlp"
+        ):
+            raise ValueError(
+                "pens_tick_path: a plain LogRegSpec or MLPSpec is required"
+            )
+        if spec.family == "mlp":
+            return self.ext.pens_mlp_tick_path(
+                list(spec.dims), spec.batch_size, data.x.shape[1]
+            )
         return self.ext.pens_tick_path(
             spec.d_in, spec.n_classes, spec.batch_size, data.x.shape[1],
         )

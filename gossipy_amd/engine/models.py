@@ -265,9 +265,15 @@ class MLPSpec(_PartitionMixin):
     ``GOSSIPY_MLP_WIDE=1`` / ``=0`` force / forbid the wide one. Evaluation
     follows the same split: ``eval_mlp`` while the row and 16 rows of forward
     scratch fit LDS, ``eval_mlp_wide`` past that, on per-node test shards of
-    at most 2048 rows (a shared set scores through torch). Still bound to the LDS budget:
-    ``n_parts``, ``sample_size`` and the PENS event, which raise a budget
-    error past it.
+    at most 2048 rows (a shared set scores through torch). The PENS step-1
+    event keeps ``tick_pens_mlp_kernel`` (``w = 1``) by default and raises a
+    budget error past it; ``GOSSIPY_PENS_MLP_WIDE=1`` selects the wide route
+    on any shape: ``pens_mlp_score_kernel`` forwards every candidate of every
+    event over a (row block, candidate) grid, ``tick_pens_mlp_wide_kernel``
+    selects, merges in place and runs the wide tick's update
+    (``HIPBackend.pens_tick_path`` tells which). Still bound to the LDS
+    budget: ``n_parts`` and ``sample_size``, which raise a budget error past
+    it.
     """
 
     d_in: int

@@ -60,6 +60,15 @@
 //                           candidates scored in one MFMA GEMM that streams
 //                           the shard once per 16 candidates, then the merge
 //                           and the wide tick's update; see pens_use_wide.
+//   pens_mlp_score_kernel, tick_pens_mlp_wide_kernel
+//                         — the MLP PENS event past the LDS budget
+//                           (784-100-10), two launches: every candidate of
+//                           every event forwarded over (row block, candidate)
+//                           blocks on eval_mlp_wide_kernel's streamed MFMA
+//                           layers, hit counts out; then per event the
+//                           selection, the in-place merge and
+//                           tick_mlp_wide_kernel's update. Opt-in, see
+//                           pens_mlp_use_wide.
 //   eval_metrics_kernel   — K13: accuracy / macro P-R-F1 / pairwise AUC of
 //                           R affine or margin models (or precomputed
 //                           scores) on a shared set or per-node shards.
@@ -2690,6 +2699,9 @@ struct PensMlpArgs {
     const int* cowners;     // candidate senders (global node ids)
     int* wins;              // [n_local, n_total] winner counters
     int m_top, n_total;
+    // tick_pens_mlp_wide_kernel only: pens_mlp_score_kernel's hits, one int
+    // per (candidate, row block)
+    const int* partial; int n_rb;
 };
 
 __global__ void __launch_bounds__(512)
@@ -3615,47 +3627,41 @@ DEV_INLINE LRW_FN void emw_store_panel(const float4 (&wreg)[EMW_WNV],
     if (xt) emw_store<emw_xnv<RB>(), VEC>(xreg, xt, RB);
 }
 
-template <int RB, bool VEC>
-__global__ LRW_FN void __launch_bounds__(EMW_THREADS)
-eval_mlp_wide_kernel(EvalMlpWideArgs p)
+// The layer loop of the wide forward: the m <= RB rows at Xb (row stride d_in)
+// through the model row prow, which starts row_off floats into an arena whose
+// base is 16-byte aligned when w_aligned is set. `sm` holds the two weight
+// tiles, the two input tiles and the two activation buffers of stride AS.
+// HEAD_LDS = false: the head's live rows go to Zb (row stride k). HEAD_LDS =
+// true: the head's [RB, k] block goes, like a hidden layer's but without the
+// ReLU, to the free activation buffer, which is returned; the caller's
+// barrier must stand before it is read (AS covers k then).
+template <int RB, bool VEC, bool HEAD_LDS>
+DEV_INLINE LRW_FN const float* emw_forward(
+    const float* prow, long row_off, bool w_aligned, const int* layout,
+    int n_layers, int d_in, const float* Xb, int m, float* sm, int AS,
+    float* Zb, int k)
 {
     constexpr int RT = RB / 16;          // row tiles of the block
     constexpr int CS = 4 / RT;           // waves that share a row tile
     constexpr int NT = EMW_CG / 16 / CS; // column tiles of a wave per pass
     constexpr int XNV = emw_xnv<RB>();
-    const int r = blockIdx.y, node = p.nodes[r];
-    const int row0 = blockIdx.x * RB;
-    int live = p.S;
-    const float* Xb = p.X;
-    if (p.eval_counts) {
-        live = min(p.eval_counts[node], p.S);
-        Xb += (long)node * p.S * p.d_in;
-    }
-    if (row0 >= live) return;
-    const int m = min(RB, live - row0);  // live rows of the block
-    Xb += (long)row0 * p.d_in;
-    float* Zb = p.Z + ((long)r * p.S + row0) * p.k;
-    const float* prow = p.params + (long)node * p.D;
-
-    extern __shared__ float sm[];
     float* wst = sm;                              // 2 x EMW_CG x EMW_LS
     float* xst = wst + 2 * EMW_CG * EMW_LS;       // 2 x RB x EMW_LS
     float* act = xst + 2 * RB * EMW_LS;           // 2 x RB x act_stride
-    const int AS = p.act_stride;
 
     const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
     const int li = lane & 15, lq = lane >> 4;
     const int rt = wave % RT, cs = wave / RT;
+    const float* out = nullptr;
 
-    for (int l = 0; l < p.n_layers; ++l) {
-        const int w_off = p.layout[4 * l], b_off = p.layout[4 * l + 1];
-        const int fin = p.layout[4 * l + 2], fout = p.layout[4 * l + 3];
-        const bool head = l == p.n_layers - 1;
+    for (int l = 0; l < n_layers; ++l) {
+        const int w_off = layout[4 * l], b_off = layout[4 * l + 1];
+        const int fin = layout[4 * l + 2], fout = layout[4 * l + 3];
+        const bool head = l == n_layers - 1;
         const float* Wl = prow + w_off;
         const float* cur = act + ((l + 1) & 1) * RB * AS;  // layer l - 1's
         float* nxt = act + (l & 1) * RB * AS;
-        const bool vw = p.w_aligned && !(fin & 3) &&
-                        !(((long)node * p.D + w_off) & 3);
+        const bool vw = w_aligned && !(fin & 3) && !((row_off + w_off) & 3);
         const int nP = (fin + EMW_KP - 1) / EMW_KP;
         for (int c0 = 0; c0 < fout; c0 += EMW_CG) {
             const int wvalid = min(EMW_CG, fout - c0);
@@ -3668,13 +3674,13 @@ eval_mlp_wide_kernel(EvalMlpWideArgs p)
             for (int j = 0; j < NT; ++j)
                 for (int q = 0; q < 4; ++q) acc[j][q] = 0.f;
             emw_load_panel<RB, VEC>(wreg, xreg, vw, Wp, fin, wvalid, wrows, Xl,
-                                    p.d_in, m, 0);
+                                    d_in, m, 0);
             emw_store_panel<RB, VEC>(wreg, xreg, vw, wst, wrows, Xl ? xst : nullptr);
             __syncthreads();
             for (int pn = 0; pn < nP; ++pn) {
                 if (pn + 1 < nP)
                     emw_load_panel<RB, VEC>(wreg, xreg, vw, Wp, fin, wvalid,
-                                            wrows, Xl, p.d_in, m, pn + 1);
+                                            wrows, Xl, d_in, m, pn + 1);
                 const float* wt =
                     wst + (pn & 1) * EMW_CG * EMW_LS + li * EMW_LS + lq;
                 const float* xt =
@@ -3715,8 +3721,10 @@ eval_mlp_wide_kernel(EvalMlpWideArgs p)
                         float v = acc[j][q] + b;
                         if (!head)
                             nxt[row * AS + col] = fmaxf(v, 0.f);
+                        else if (HEAD_LDS)
+                            nxt[row * AS + col] = v;
                         else if (row < m)
-                            Zb[(long)row * p.k + col] = v;
+                            Zb[(long)row * k + col] = v;
                     }
                 }
             }
@@ -3724,7 +3732,169 @@ eval_mlp_wide_kernel(EvalMlpWideArgs p)
             // left at the loop's last barrier; nxt is read after the next
             // layer's first barrier
         }
+        out = nxt;
     }
+    return out;
+}
+
+template <int RB, bool VEC>
+__global__ LRW_FN void __launch_bounds__(EMW_THREADS)
+eval_mlp_wide_kernel(EvalMlpWideArgs p)
+{
+    const int r = blockIdx.y, node = p.nodes[r];
+    const int row0 = blockIdx.x * RB;
+    int live = p.S;
+    const float* Xb = p.X;
+    if (p.eval_counts) {
+        live = min(p.eval_counts[node], p.S);
+        Xb += (long)node * p.S * p.d_in;
+    }
+    if (row0 >= live) return;
+    const int m = min(RB, live - row0);  // live rows of the block
+    extern __shared__ float sm[];
+    emw_forward<RB, VEC, false>(
+        p.params + (long)node * p.D, (long)node * p.D, p.w_aligned, p.layout,
+        p.n_layers, p.d_in, Xb + (long)row0 * p.d_in, m, sm, p.act_stride,
+        p.Z + ((long)r * p.S + row0) * p.k, p.k);
+}
+
+// ---------------------------------------------------------------------------
+// wide MLP PENS step-1 event: two launches for the models whose row misses
+// the LDS of tick_pens_mlp_kernel (784-100-10), neither with an LDS term that
+// grows with D or with rows * d_in.
+//
+// pens_mlp_score_kernel, grid (ceil(Smax / RB), candidates of ALL events):
+// block (rb, j) forwards RB rows of the shard of candidate j's receiver
+// through candidate j's model, slots[cslots[j]], with emw_forward: the
+// candidates of every event spread over the machine, where the LDS kernel
+// scores one receiver's candidates one after another on one CU. The head
+// block stays in LDS: thread s takes the arg-max of row s (ascending scan,
+// strict >, the first maximum wins, as torch.argmax and the LDS kernel),
+// compares it with the label, and the block's hits are summed by wave
+// shuffles and a few LDS ints into partial[j * n_rb + rb]. Every block
+// writes its int (0 at or past the receiver's live count), so there is no
+// atomic and no zeroing pass, and a count depends on the inputs alone.
+//
+// tick_pens_mlp_wide_kernel, one block per event: sums the partials of each
+// candidate, selects with pens_select, merges in place on params[node]
+// (private to the block: receivers are unique within a launch) with the
+// LDS kernel's arithmetic in its order, and runs mlp_update<false, true> as
+// tick_mlp_wide_kernel does (act / grad in LDS, or ACT_WS in the block's
+// workspace row). Given equal counts its result is bit-equal to
+// tick_pens_mlp_kernel's.
+// ---------------------------------------------------------------------------
+
+struct PensMlpScoreArgs {
+    const float* slots;      // [n_slots, D] candidate models
+    const int* cslots;       // [C] candidate slots, all events, arrival order
+    const int* cand_event;   // [C] event of a candidate
+    const int* nodes;        // [E] event receivers
+    const float* X; const float* Y; const int* dcounts;
+    const int* layout;       // [n_layers][4] = (w_off, b_off, in, out)
+    int* partial;            // [C, n_rb] hits of a block
+    int n_layers, D, d_in, Smax, k, n_rb;
+    int act_stride;          // covers the widest output, the head included
+    int w_aligned;           // slots is 16-byte aligned
+};
+
+template <int RB, bool VEC>
+__global__ LRW_FN void __launch_bounds__(EMW_THREADS)
+pens_mlp_score_kernel(PensMlpScoreArgs p)
+{
+    const int rb = blockIdx.x, j = blockIdx.y, tid = threadIdx.x;
+    const int node = p.nodes[p.cand_event[j]];
+    const int live = min(p.dcounts[node], p.Smax);
+    const int row0 = rb * RB;
+    int* out = p.partial + (long)j * p.n_rb + rb;
+    if (row0 >= live) {
+        if (tid == 0) *out = 0;
+        return;
+    }
+    const int m = min(RB, live - row0);  // live rows of the block
+    const long slot = p.cslots[j];
+    extern __shared__ float sm[];
+    __shared__ int wave_hits[EMW_THREADS / WAVE];
+    const float* head = emw_forward<RB, VEC, true>(
+        p.slots + slot * p.D, slot * p.D, p.w_aligned, p.layout, p.n_layers,
+        p.d_in, p.X + ((long)node * p.Smax + row0) * p.d_in, m, sm,
+        p.act_stride, nullptr, p.k);
+    __syncthreads();
+    int hit = 0;
+    if (tid < m) {
+        const float* z = head + tid * p.act_stride;
+        float best = z[0];
+        int bj = 0;
+        for (int kk = 1; kk < p.k; ++kk) {
+            if (z[kk] > best) { best = z[kk]; bj = kk; }
+        }
+        hit = bj == (int)p.Y[(long)node * p.Smax + row0 + tid];
+    }
+    for (int off = WAVE / 2; off > 0; off >>= 1)
+        hit += __shfl_down(hit, off, WAVE);
+    if ((tid & (WAVE - 1)) == 0) wave_hits[tid / WAVE] = hit;
+    __syncthreads();
+    if (tid == 0) {
+        int s = 0;
+        for (int w = 0; w < EMW_THREADS / WAVE; ++w) s += wave_hits[w];
+        *out = s;
+    }
+}
+
+template <bool ACT_WS>
+__global__ void __launch_bounds__(512)
+tick_pens_mlp_wide_kernel(PensMlpArgs p)
+{
+    const MlpArgs& a = p.m;
+    int i = blockIdx.x;
+    int node = a.nodes[i];
+    int tid = threadIdx.x;
+    int lo = a.ptr[i], hi = a.ptr[i + 1];
+    int n_cand = hi - lo;
+    extern __shared__ float sm[];
+    __shared__ int correct[PENS_MAX_CAND];
+    __shared__ int sel[PENS_MAX_CAND];
+    float* W = a.params + (long)node * a.D;
+    float* act;
+    if constexpr (ACT_WS) act = a.ws + (long)i * a.ws_row;
+    else act = sm;
+    int bsmax = (a.bs == 0) ? a.Smax : min(a.bs, a.Smax);
+    int act_total = 0;
+    for (int l = 0; l < a.n_layers; ++l) act_total += a.layout[4 * l + 3];
+    float* grad = act + (long)bsmax * act_total;
+
+    // --- the scorer's hits per candidate, row blocks in ascending order
+    for (int c = tid; c < n_cand; c += blockDim.x) {
+        const int* part = p.partial + (long)(lo + c) * p.n_rb;
+        int s = 0;
+        for (int rb = 0; rb < p.n_rb; ++rb) s += part[rb];
+        correct[c] = s;
+    }
+    __syncthreads();
+    if (tid == 0)
+        pens_select(correct, sel, n_cand, p.m_top,
+                    p.wins + (long)node * p.n_total, p.cowners + lo);
+    __syncthreads();
+
+    // --- merge: (own + sum selected) / (n_sel+1), age = max, in place; each
+    //     thread owns its elements of W throughout, so no barrier until the
+    //     end
+    int n_sel = 0;
+    int age = a.ages[node];
+    for (int c = 0; c < n_cand; ++c) {
+        if (!sel[c]) continue;
+        n_sel += 1;
+        int slot = p.cslots[lo + c];
+        const float* Wc = a.slots + (long)slot * a.D;
+        for (int e = tid; e < a.D; e += blockDim.x) W[e] += Wc[e];
+        age = max(age, a.slot_ages[slot]);
+    }
+    float inv = 1.0f / (n_sel + 1);
+    for (int e = tid; e < a.D; e += blockDim.x) W[e] *= inv;
+    __syncthreads();
+
+    // --- local update on the row in device memory
+    mlp_update<false, true>(a, node, W, act, grad, age);
+    if (tid == 0) a.ages[node] = age;
 }
 
 // ---------------------------------------------------------------------------
@@ -4434,6 +4604,7 @@ struct MlpGeom {
     // no dX of layer 0: the layers' outputs + two buffers of the widest one
     size_t wide_scratch;
     int out_max;
+    int head;  // outputs of the last layer
 };
 
 constexpr size_t LDS_BUDGET = 160 * 1024;
@@ -4507,6 +4678,7 @@ static MlpGeom mlp_fill(MlpArgs& a, const StateTensors& st,
     g.scratch = mlp_scratch(bsmax, a.d_in, act_sum, act_max, false);
     g.wide_scratch = mlp_scratch(bsmax, a.d_in, act_sum, out_max, true);
     g.out_max = out_max;
+    g.head = Lh[4 * (n_layers - 1) + 3];
     // block size: 8 waves when any GEMM stage has >= 8 MFMA tiles (halves
     // the sequential tile passes of the widest stage — e.g. dW [100,57] is
     // 28 tiles), else the default 4 waves
@@ -5188,14 +5360,149 @@ void tick_pens(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
                        a);
 }
 
+static int64_t eval_mlp_wide_stride(int64_t max_hidden);
+static size_t eval_mlp_wide_smem(int64_t rb, int64_t max_hidden);
+
+constexpr size_t PENS_STATIC_LDS = 2 * sizeof(int) * PENS_MAX_CAND;
+
+// Which route serves an MLP PENS event whose LDS-resident plan needs `smem`
+// bytes of dynamic LDS: tick_pens_mlp_kernel, unless GOSSIPY_PENS_MLP_WIDE=1
+// selects the wide route (pens_mlp_score_kernel + tick_pens_mlp_wide_kernel)
+// on any shape. The wide route is opt-in: unset or 0, a shape past the budget
+// raises the budget error.
+static bool pens_mlp_use_wide(size_t smem)
+{
+    const char* v = getenv("GOSSIPY_PENS_MLP_WIDE");
+    if (v && *v && atoi(v) != 0) return true;
+    TORCH_CHECK(smem + PENS_STATIC_LDS <= LDS_BUDGET,
+        "pens mlp LDS budget exceeded (", smem,
+        " B of dynamic LDS); shrink batch_size/hidden. The global-resident"
+        " wide kernel covers the plain MLP tick only; GOSSIPY_PENS_MLP_WIDE=1"
+        " selects the wide PENS route, which streams the candidates");
+    return false;
+}
+
+// Rows of a block of pens_mlp_score_kernel by the rule of eval_mlp_wide_rb:
+// the largest of 64, 32 and 16 whose staging tiles and two activation
+// buffers, as wide as the widest layer output, fit the LDS budget. Raises
+// when a hidden layer is too wide for 16 rows.
+static int64_t pens_mlp_score_rb(int64_t out_max)
+{
+    for (int64_t rb : {64, 32, 16})
+        if (eval_mlp_wide_smem(rb, out_max) + sizeof(int) * 4 <= LDS_BUDGET)
+            return rb;
+    TORCH_CHECK(false, "pens mlp wide LDS budget exceeded (",
+        eval_mlp_wide_smem(16, out_max), " B for blocks of 16 rows): the"
+        " scorer keeps two activation buffers as wide as the widest layer (",
+        out_max, " outputs) in LDS; shrink hidden");
+    return 0;
+}
+
+// "lds" or "wide": the route tick_pens_mlp takes for an MLP of layer widths
+// `dims` (d_in, hidden..., n_classes) on shards of stride Smax
+static std::string pens_mlp_tick_path(std::vector<int64_t> dims, int64_t bs,
+                                      int64_t Smax)
+{
+    TORCH_CHECK(dims.size() >= 2, "dims must hold d_in and n_classes");
+    int64_t D = 0, out_sum = 0, width_max = dims[0], out_max = 0;
+    for (size_t l = 0; l + 1 < dims.size(); ++l) {
+        D += dims[l + 1] * dims[l] + dims[l + 1];
+        out_sum += dims[l + 1];
+        width_max = std::max(width_max, dims[l + 1]);
+        out_max = std::max(out_max, dims[l + 1]);
+    }
+    size_t smem = sizeof(float) *
+                  ((size_t)D + mlp_scratch(batch_rows(bs, (int)Smax), dims[0],
+                                           out_sum, width_max, false));
+    if (!pens_mlp_use_wide(smem)) return "lds";
+    pens_mlp_score_rb(out_max);  // raises when the scorer misses the budget
+    return "wide";
+}
+
+// hits of pens_mlp_score_kernel's blocks, one buffer per (device, stream):
+// grown, never shrunk or freed, as mlp_wide_workspace
+static int* pens_mlp_partials(const torch::Device& dev, size_t ints)
+{
+    static auto* cache =
+        new std::map<std::pair<int, hipStream_t>, torch::Tensor>();
+    torch::Tensor& t = (*cache)[{(int)dev.index(), current_stream()}];
+    if (!t.defined() || (size_t)t.numel() < ints)
+        t = torch::empty({(int64_t)ints},
+                         torch::dtype(torch::kInt32).device(dev));
+    return t.data_ptr<int>();
+}
+
+template <bool VEC>
+static void (*pens_mlp_score_pick(int64_t rb))(PensMlpScoreArgs)
+{
+    return rb == 64   ? pens_mlp_score_kernel<64, VEC>
+           : rb == 32 ? pens_mlp_score_kernel<32, VEC>
+                      : pens_mlp_score_kernel<16, VEC>;
+}
+
+// The wide route of tick_pens_mlp: the scorer over (row block, candidate),
+// then one block per event. `p` comes filled for the LDS kernel.
+static void tick_pens_mlp_wide(PensMlpArgs& p, const MlpGeom& g, int n,
+                               const torch::Tensor& cslots,
+                               const torch::Tensor& cand_event,
+                               const torch::Device& dev)
+{
+    MlpArgs& a = p.m;
+    int64_t C = cslots.size(0);
+    CHECK_DEV(cand_event);
+    TORCH_CHECK(cand_event.scalar_type() == torch::kInt32 &&
+                cand_event.size(0) == C,
+                "cand_event must hold one int32 event index per candidate");
+    int64_t rb = pens_mlp_score_rb(g.out_max);
+    // the update: act / grad in LDS, or in the block's workspace row when a
+    // batch's worth misses the budget (mlp_plan's wide branch without W2)
+    a.act_max = g.out_max;
+    bool act_ws = sizeof(float) * g.wide_scratch + PENS_STATIC_LDS > LDS_BUDGET;
+    a.ws_row = act_ws ? (long)g.wide_scratch : 0;
+    size_t ws_bytes = sizeof(float) * (size_t)a.ws_row * n;
+    TORCH_CHECK(ws_bytes <= ((size_t)1 << 34),
+        "pens mlp wide workspace too large: ", n, " events x ", a.ws_row,
+        " floats (a batch's activations and gradients) = ", ws_bytes,
+        " B > 16 GiB; shrink batch_size/hidden");
+    a.ws = act_ws ? mlp_wide_workspace(dev, (size_t)a.ws_row * n) : nullptr;
+
+    PensMlpScoreArgs s{};
+    s.slots = a.slots; s.nodes = a.nodes;
+    s.X = a.X; s.Y = a.Y; s.dcounts = a.counts; s.layout = a.layout;
+    s.n_layers = a.n_layers; s.D = a.D; s.d_in = a.d_in; s.Smax = a.Smax;
+    s.k = g.head; s.n_rb = (a.Smax + rb - 1) / rb;
+    s.act_stride = eval_mlp_wide_stride(g.out_max);
+    s.w_aligned = (uintptr_t)s.slots % 16 == 0;
+    int* partial = pens_mlp_partials(dev, (size_t)C * s.n_rb);
+    // 16-byte loads need every shard row to start on such a boundary
+    bool vec = a.d_in % 4 == 0 && (uintptr_t)a.X % 16 == 0;
+    auto score = vec ? pens_mlp_score_pick<true>(rb)
+                     : pens_mlp_score_pick<false>(rb);
+    size_t score_smem = eval_mlp_wide_smem(rb, g.out_max);
+    // a grid's y extent ends at 65535
+    for (int64_t j0 = 0; j0 < C; j0 += 65535) {
+        s.cslots = cslots.data_ptr<int>() + j0;
+        s.cand_event = cand_event.data_ptr<int>() + j0;
+        s.partial = partial + j0 * s.n_rb;
+        dim3 grid((unsigned)s.n_rb, (unsigned)std::min<int64_t>(65535, C - j0));
+        launch_kernel(score, grid, EMW_THREADS, score_smem, current_stream(),
+                      s);
+    }
+    p.partial = partial; p.n_rb = s.n_rb;
+    launch_kernel(act_ws ? tick_pens_mlp_wide_kernel<true>
+                         : tick_pens_mlp_wide_kernel<false>,
+                  n, g.threads, act_ws ? 0 : sizeof(float) * g.wide_scratch,
+                  current_stream(), p);
+}
+
 void tick_pens_mlp(torch::Tensor params, torch::Tensor ages,
                    torch::Tensor slots, torch::Tensor slot_ages,
                    torch::Tensor nodes, torch::Tensor ptr,
                    torch::Tensor cslots, torch::Tensor cowners,
-                   torch::Tensor counts, torch::Tensor X, torch::Tensor Y,
-                   torch::Tensor dcounts, torch::Tensor layout,
-                   int64_t n_layers, int64_t m_top, double lr, double wd,
-                   int64_t epochs, int64_t bs)
+                   torch::Tensor cand_event, torch::Tensor counts,
+                   torch::Tensor X, torch::Tensor Y, torch::Tensor dcounts,
+                   torch::Tensor layout, int64_t n_layers, int64_t m_top,
+                   double lr, double wd, int64_t epochs, int64_t bs)
 {
     CHECK_DEV(counts);
     int n = nodes.size(0);
@@ -5212,10 +5519,10 @@ void tick_pens_mlp(torch::Tensor params, torch::Tensor ages,
     // LDS: ONE model slab + activations + 2 grad buffers, next to the
     // kernel's static correct[] / sel[]
     size_t smem = sizeof(float) * ((size_t)p.m.D + g.scratch);
-    TORCH_CHECK(smem + 2 * sizeof(int) * PENS_MAX_CAND <= 160 * 1024,
-        "pens mlp LDS budget exceeded (", smem,
-        " B of dynamic LDS); shrink batch_size/hidden. The global-resident"
-        " wide kernel covers the plain MLP tick only");
+    if (pens_mlp_use_wide(smem)) {
+        tick_pens_mlp_wide(p, g, n, cslots, cand_event, params.device());
+        return;
+    }
     launch_kernel(tick_pens_mlp_kernel, n, g.threads, smem, current_stream(),
                   p);
 }
@@ -6190,7 +6497,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           "PENS step-1 event: score candidates, merge top-m, count winners");
     m.def("tick_pens_mlp", &tick_pens_mlp,
           "PENS step-1 event, MLP family: MFMA forward scoring of the"
-          " candidates, top-m merge, MLP SGD");
+          " candidates, top-m merge, MLP SGD; cand_event (the event of each"
+          " candidate) after cowners, read by the wide route");
+    m.def("pens_mlp_tick_path", &pens_mlp_tick_path,
+          "\"lds\" or \"wide\": the route of an MLP PENS event (dims, bs,"
+          " Smax); host code, no GPU needed");
     // most candidates one PENS event may carry (tick_pens, tick_pens_mlp)
     m.attr("PENS_MAX_CAND") = PENS_MAX_CAND;
     m.def("eval_metrics", &eval_metrics,
