@@ -20,6 +20,13 @@ candidate of every event over a (row block, candidate) grid, and
 ``tick_pens_mlp_wide_kernel`` selects, merges and updates. The script then
 prints the PENS event path as well.
 
+``--n-parts P`` and ``--sample-size F`` run partitioned and sampled gossip
+(Hegedűs 2021). Their LDS kernel cannot hold a 784-100-10 row either, so the
+script selects ``tick_mlp_comp_wide_kernel`` (``GOSSIPY_MLP_COMP_WIDE=1``
+unless the variable is already set), which works on the rows in device
+memory, merges a partition as coalesced column bands and a sample behind an
+LDS bitmap. The tick path printed is then that of the compressed tick.
+
 ``--hidden`` sets the hidden widths, ``--mode`` the CreateModelMode,
 ``--test-shards`` gives every node a test split of its own in place of the
 shared set. The script prints the tick path the configuration gets and the
@@ -67,9 +74,20 @@ def main():
     ap.add_argument("--pens", action="store_true",
                     help="PENS neighbour selection (MERGE_UPDATE only), on"
                          " the wide route of the step-1 event")
+    ap.add_argument("--n-parts", type=int, default=0, metavar="P",
+                    help="partitioned gossip over P partitions, on the wide"
+                         " compressed kernel")
+    ap.add_argument("--sample-size", type=float, default=0.0, metavar="F",
+                    help="sampled gossip over a fraction F of the parameters,"
+                         " on the wide compressed kernel")
     args = ap.parse_args()
+    comp = args.n_parts > 0 or args.sample_size > 0
+    if comp and args.pens:
+        ap.error("--pens needs whole-model gossip")
     if args.pens:
         os.environ.setdefault("GOSSIPY_PENS_MLP_WIDE", "1")
+    if comp:
+        os.environ.setdefault("GOSSIPY_MLP_COMP_WIDE", "1")
 
     device = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
     n, d, k = args.nodes, 784, 10
@@ -89,7 +107,8 @@ def main():
         )
     spec = MLPSpec(
         d_in=d, n_classes=k, hidden=tuple(args.hidden), lr=0.1,
-        batch_size=32, mode=MODES[args.mode],
+        batch_size=32, mode=MODES[args.mode], n_parts=args.n_parts,
+        sample_size=args.sample_size,
     )
     cfg = EngineConfig(
         n_nodes=n,
@@ -99,6 +118,8 @@ def main():
         sync=False,
         sampling_eval=0.1,
         seed=42,
+        n_parts=args.n_parts,
+        sampled=args.sample_size > 0,
     )
     if args.pens:
         sim = BatchedPENSGossipSimulator(
@@ -108,7 +129,12 @@ def main():
     else:
         sim = BatchedGossipSimulator(cfg, spec, data, device=device)
     hip = sim.backend.name == "hip"
-    path = sim.backend.mlp_tick_path(spec, data) if hip else "torch (no GPU)"
+    if not hip:
+        path = "torch (no GPU)"
+    elif comp:
+        path = sim.backend.mlp_comp_tick_path(spec, data)
+    else:
+        path = sim.backend.mlp_tick_path(spec, data)
     print(f"MLP {'-'.join(map(str, spec.dims))}, D = {spec.D}: tick path {path}")
     if args.pens:
         path = sim.backend.pens_tick_path(spec, data) if hip else "torch (no GPU)"

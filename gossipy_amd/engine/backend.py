@@ -404,7 +404,8 @@ class TorchBackend:
                     g = torch.empty_like(row)
                     g[: k * d] = (dz.t() @ xb).reshape(-1)
                     g[k * d :] = dz.sum(0)
-                    g /= ages[idx].float()[apart]
+                    # (reshape: one partition's ages are a flat [n])
+                    g /= ages[idx].float().reshape(-1)[apart]
                     if spec.weight_decay:
                         g += spec.weight_decay * row
                     row -= spec.lr * g
@@ -449,7 +450,8 @@ class TorchBackend:
                         g[b_off : b_off + fout] = dh.sum(0)
                         if li > 0:
                             dh = (dh @ layers[li][0]) * (acts[li] > 0).float()
-                    g /= ages[idx].float()[apart]
+                    # (reshape: one partition's ages are a flat [n])
+                    g /= ages[idx].float().reshape(-1)[apart]
                     if spec.weight_decay:
                         g += spec.weight_decay * row
                     row -= spec.lr * g
@@ -459,17 +461,18 @@ class TorchBackend:
         (gossipy/model/handler.py:497-501 + gossipy/model/sampling.py:201-234)."""
         perm, ptr, _ = self._part(spec, state.params.device)
         idx = perm[int(ptr[pid]) : int(ptr[pid + 1])]
-        w1 = int(state.ages[node, pid])
-        w2 = int(pool.slot_ages[slot, pid])
+        # ages are [n, P], flat [n] for a single partition
+        ages = state.ages.view(len(state.ages), -1)
+        slot_ages = pool.slot_ages.view(len(pool.slot_ages), -1)
+        w1 = int(ages[node, pid])
+        w2 = int(slot_ages[slot, pid])
         if (w1, w2) == (0, 0):
             w1 = w2 = 1
         m1, m2 = w1 / (w1 + w2), w2 / (w1 + w2)
         state.params[node, idx] = (
             m1 * state.params[node, idx] + m2 * pool.slots[slot, idx]
         )
-        state.ages[node, pid] = max(
-            int(state.ages[node, pid]), int(pool.slot_ages[slot, pid])
-        )
+        ages[node, pid] = max(int(ages[node, pid]), int(slot_ages[slot, pid]))
 
     def _deliver_part(
         self, state, pool, data, spec, recv_nodes, recv_ptr, del_slots,
@@ -1872,14 +1875,38 @@ class HIPBackend(TorchBackend):
         fits, else ``"wide"`` (``tick_mlp_wide_kernel``: rows in device
         memory, the minibatch read from the arena). ``GOSSIPY_MLP_WIDE=1``
         forces ``"wide"``; with ``=0`` a shape past the budget raises the
-        budget error instead. Partitioned and sampled MLP ticks have the LDS
-        kernels only; the PENS event has a split and a knob of its own, see
-        ``pens_tick_path``."""
+        budget error instead. Partitioned and sampled MLP ticks and the PENS
+        event have splits and knobs of their own, see ``mlp_comp_tick_path``
+        and ``pens_tick_path``."""
         if spec.family != "mlp" or spec.n_parts > 0 or spec.sample_size > 0:
             raise ValueError("mlp_tick_path: a plain MLPSpec is required")
         return self.ext.mlp_tick_path(
             list(spec.dims), spec.batch_size, data.x.shape[1],
             _MODE_ID[spec.mode],
+        )
+
+    def mlp_comp_tick_path(self, spec, data) -> str:
+        """Which kernel the partitioned (``n_parts > 0``) or sampled
+        (``sample_size > 0``) MLP tick of ``spec`` runs on the shards of
+        ``data``: ``"lds"`` (``tick_mlp_comp_kernel``: the model row, a
+        second slab unless MERGE_UPDATE, the sampled pre-merge copy, the
+        staged minibatch and the activations in one workgroup's 160 KB of
+        LDS) or ``"wide"`` (``tick_mlp_comp_wide_kernel``: rows in device
+        memory, the partition merged as column bands, the sample behind an
+        LDS bitmap; the same bits on a shape both take). The wide kernel is
+        opt-in: ``GOSSIPY_MLP_COMP_WIDE=1`` selects it on any shape; unset
+        or ``0`` a shape past the budget (784-100-10) raises the budget
+        error, which names the knob."""
+        part = spec.n_parts > 0
+        if spec.family != "mlp" or not (part or spec.sample_size > 0):
+            raise ValueError(
+                "mlp_comp_tick_path: a partitioned or sampled MLPSpec is"
+                " required"
+            )
+        return self.ext.mlp_comp_tick_path(
+            list(spec.dims), spec.batch_size, data.x.shape[1],
+            _MODE_ID[spec.mode], spec.n_parts if part else 0,
+            0 if part else spec.samp_count(),
         )
 
     def mlp_eval_path(self, spec, n_eval) -> str:

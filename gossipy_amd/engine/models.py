@@ -271,9 +271,14 @@ class MLPSpec(_PartitionMixin):
     on any shape: ``pens_mlp_score_kernel`` forwards every candidate of every
     event over a (row block, candidate) grid, ``tick_pens_mlp_wide_kernel``
     selects, merges in place and runs the wide tick's update
-    (``HIPBackend.pens_tick_path`` tells which). Still bound to the LDS
-    budget: ``n_parts`` and ``sample_size``, which raise a budget error past
-    it.
+    (``HIPBackend.pens_tick_path`` tells which). ``n_parts`` and
+    ``sample_size`` keep ``tick_mlp_comp_kernel`` (the row, a second slab
+    unless MERGE_UPDATE and the sampled pre-merge copy in LDS) by default and
+    raise a budget error past it; ``GOSSIPY_MLP_COMP_WIDE=1`` selects
+    ``tick_mlp_comp_wide_kernel`` on any shape: rows in device memory, the
+    partition merged as coalesced column bands, the sample behind an LDS
+    bitmap of one bit per parameter, the same bits on a shape both take
+    (``HIPBackend.mlp_comp_tick_path`` tells which).
     """
 
     d_in: int

@@ -28,6 +28,12 @@
 //   tick_mlp_comp_kernel  — the MLP tick under partitioned / sampled
 //                           gossip (gossipy/model/handler.py:426-525),
 //                           same SGD body, templated on the merge policy.
+//   tick_mlp_comp_wide_kernel
+//                         — the compressed MLP tick past the LDS budget
+//                           (784-100-10): rows in device memory, the
+//                           partition merged as coalesced column bands, the
+//                           sample merged behind an LDS bitmap of the indices
+//                           already written. Opt-in, see mlp_comp_use_wide.
 //   tick_logreg_lim_kernel, tick_mlp_kernel<true>
 //                         — the logreg / MLP ticks with the limited merge
 //                           (LimitedMergeMixin._merge,
@@ -2230,6 +2236,186 @@ tick_mlp_comp_kernel(MlpCompArgs c)
     __syncthreads();
     for (int e = tid; e < a.D; e += blockDim.x)
         a.params[(long)node * a.D + e] = W[e];
+    if constexpr (PART) {
+        for (int p = tid; p < P; p += blockDim.x)
+            a.ages[(long)node * P + p] = agev[p];
+    } else {
+        if (tid == 0) a.ages[node] = age;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// compressed MLP ticks past the LDS budget: tick_mlp_comp_kernel's delivery
+// semantics, line by line, on tick_mlp_wide_kernel's operand placement. No
+// LDS term scales with D or with batch_rows * d_in:
+//   W     is params[node] itself, worked on in place (receivers are unique
+//         within a launch);
+//   W2    (UPDATE / UPDATE_MERGE's trained copy of the received model) is the
+//         head of this block's row of the device workspace a.ws;
+//   act / grad as in tick_mlp_wide_kernel: LDS, or (ACT_WS) behind W2;
+//   agev / agev2 (PART) and the sampled merge's bitmap stay in LDS.
+// SGD is mlp_update<PART, true>, so a shape both kernels take returns the
+// LDS kernel's bits. The merges are the part with a design of their own: an
+// arena row has neither LDS's free scattered access (the perm walk touches a
+// cache line per element) nor its cheap D-float copy (the sampled W3).
+// ---------------------------------------------------------------------------
+
+// mlp_part_merge without the perm table. Partition `pid` is the range
+// [pptr[pid], pptr[pid+1]) of the Fortran-flat order, in which a layer's
+// block starts where it starts in the arena row (both advance by
+// fin*fout + fout per layer) and holds the weights column by column,
+// t = col * fout + row, then the biases. The range therefore meets a layer
+// in at most one run [t0, t1) of weight positions, a band of whole columns
+// with a ragged first and last one, and one contiguous run of biases. The
+// band is walked row by row with the lanes along its columns, which is
+// contiguous in the row-major arena row and in src, and masked by t.
+DEV_INLINE void mlp_part_merge_wide(const MlpCompArgs& c, float* W, int* agev,
+                                    const float* src, const int* src_ages,
+                                    int pid)
+{
+    const MlpArgs& a = c.m;
+    int tid = threadIdx.x;
+    int w1 = agev[pid], w2 = src_ages[pid];
+    float m1, m2;
+    if (w1 == 0 && w2 == 0) { m1 = 0.5f; m2 = 0.5f; }
+    else {
+        float s = (float)(w1 + w2);
+        m1 = (float)w1 / s;
+        m2 = (float)w2 / s;
+    }
+    int g0 = c.pptr[pid], g1 = c.pptr[pid + 1];
+    __syncthreads();
+    for (int l = 0; l < a.n_layers; ++l) {
+        int w_off = a.layout[4 * l], b_off = a.layout[4 * l + 1];
+        int fin = a.layout[4 * l + 2], fout = a.layout[4 * l + 3];
+        int t0 = max(g0 - w_off, 0), t1 = min(g1 - w_off, fin * fout);
+        if (t0 < t1) {
+            int c0 = t0 / fout, bw = (t1 - 1) / fout + 1 - c0;
+            for (int e = tid; e < fout * bw; e += blockDim.x) {
+                int row = e / bw, col = c0 + e % bw;
+                int t = col * fout + row;
+                if (t >= t0 && t < t1) {
+                    int i = w_off + row * fin + col;
+                    W[i] = m1 * W[i] + m2 * src[i];
+                }
+            }
+        }
+        int b1 = min(g1 - b_off, fout);
+        for (int e = max(g0 - b_off, 0) + tid; e < b1; e += blockDim.x)
+            W[b_off + e] = m1 * W[b_off + e] + m2 * src[b_off + e];
+    }
+    if (tid == 0) agev[pid] = max(w1, w2);
+    __syncthreads();
+}
+
+// mlp_samp_merge without the pre-merge copy W3, a 2*D-float round trip per
+// delivery on an arena row. `seen` is a bitmap of ceil(D/32) LDS words,
+// cleared per delivery: the thread whose atomicOr finds the bit of index i
+// clear is the only one to write W[i], so it reads the pre-merge value, and
+// the duplicates it shuts out would have stored the same value. The result
+// depends on the inputs alone.
+DEV_INLINE void mlp_samp_merge_wide(const MlpCompArgs& c, float* W,
+                                    unsigned* seen, const float* src, int seed)
+{
+    int tid = threadIdx.x;
+    int D = c.m.D;
+    for (int e = tid; e < (D + 31) >> 5; e += blockDim.x) seen[e] = 0u;
+    __syncthreads();
+    for (int q = tid; q < c.samp_c; q += blockDim.x) {
+        int i = (int)(splitmix64_dev((unsigned long long)seed +
+                                     (unsigned long long)q) %
+                      (unsigned long long)D);
+        unsigned bit = 1u << (i & 31);
+        if (!(atomicOr(&seen[i >> 5], bit) & bit))
+            W[i] = 0.5f * (W[i] + src[i]);
+    }
+    __syncthreads();
+}
+
+template <bool PART, bool ACT_WS>
+__global__ void __launch_bounds__(512)
+tick_mlp_comp_wide_kernel(MlpCompArgs c)
+{
+    const MlpArgs& a = c.m;
+    int i = blockIdx.x;
+    int node = a.nodes[i];
+    int tid = threadIdx.x;
+    extern __shared__ float sm[];
+    // LDS (host computes the same sum): act | 2 grad buffers unless ACT_WS,
+    // then agev, agev2 (PART) or the bitmap (sampled)
+    float* W = a.params + (long)node * a.D;
+    float* wsrow = a.ws + (long)i * a.ws_row;
+    bool has_w2 = (a.mode != MODE_MERGE_UPDATE);
+    float* W2 = has_w2 ? wsrow : nullptr;
+    int bsmax = (a.bs == 0) ? a.Smax : min(a.bs, a.Smax);
+    int act_total = 0;
+    for (int l = 0; l < a.n_layers; ++l) act_total += a.layout[4 * l + 3];
+    float* act;
+    float* tail = sm;
+    if constexpr (ACT_WS) {
+        act = wsrow + (has_w2 ? a.D : 0);
+    } else {
+        act = sm;
+        tail = sm + (long)bsmax * (act_total + 2 * a.act_max);
+    }
+    float* grad = act + (long)bsmax * act_total;
+    int* agev = (int*)tail;               // P                (PART)
+    int* agev2 = agev + c.P;              // P                (PART)
+    unsigned* seen = (unsigned*)tail;     // ceil(D/32)       (sampled)
+    const int P = PART ? c.P : 0;
+
+    for (int p = tid; p < P; p += blockDim.x)
+        agev[p] = a.ages[(long)node * P + p];
+    __syncthreads();
+    int age = PART ? 0 : a.ages[node];
+
+    if (a.update_only) {
+        mlp_update<PART, true>(a, node, W, act, grad, age, agev, c.apart, P);
+    } else {
+        for (int j = a.ptr[i]; j < a.ptr[i + 1]; ++j) {
+            int slot = a.dslots[j];
+            int pid = c.dpids ? c.dpids[j] : 0;  // partition id / seed
+            const float* srow = a.slots + (long)slot * a.D;
+            if (a.mode == MODE_MERGE_UPDATE) {
+                if constexpr (PART)
+                    mlp_part_merge_wide(c, W, agev, srow,
+                                        a.slot_ages + (long)slot * P, pid);
+                else
+                    mlp_samp_merge_wide(c, W, seen, srow, pid);
+                mlp_update<PART, true>(a, node, W, act, grad, age, agev,
+                                       c.apart, P);
+            } else {
+                // UPDATE / UPDATE_MERGE as in tick_mlp_comp_kernel
+                if (a.mode == MODE_UPDATE_MERGE)
+                    mlp_update<PART, true>(a, node, W, act, grad, age, agev,
+                                           c.apart, P);
+                for (int e = tid; e < a.D; e += blockDim.x) W2[e] = srow[e];
+                for (int p = tid; p < P; p += blockDim.x)
+                    agev2[p] = a.slot_ages[(long)slot * P + p];
+                __syncthreads();
+                int age2 = 0;
+                mlp_update<PART, true>(a, node, W2, act, grad, age2, agev2,
+                                       c.apart, P);
+                if constexpr (PART)
+                    mlp_part_merge_wide(c, W, agev, W2, agev2, pid);
+                else
+                    mlp_samp_merge_wide(c, W, seen, W2, pid);
+            }
+            int rs = a.rslots ? a.rslots[j] : -1;
+            if (rs >= 0) {
+                for (int e = tid; e < a.D; e += blockDim.x)
+                    a.slots[(long)rs * a.D + e] = W[e];
+                if constexpr (PART) {
+                    for (int p = tid; p < P; p += blockDim.x)
+                        a.slot_ages[(long)rs * P + p] = agev[p];
+                } else {
+                    if (tid == 0) a.slot_ages[rs] = age;
+                }
+                __syncthreads();
+            }
+        }
+    }
+    __syncthreads();
     if constexpr (PART) {
         for (int p = tid; p < P; p += blockDim.x)
             a.ages[(long)node * P + p] = agev[p];
@@ -4762,10 +4948,53 @@ static std::string mlp_tick_path(std::vector<int64_t> dims, int64_t bs,
     return mlp_use_wide(lds) ? "wide" : "lds";
 }
 
-// Partitioned (part) or sampled compressed MLP. Checks the per-mode LDS
-// budget: W, +W2 unless MERGE_UPDATE, +the sampled pre-merge copy unless it
-// fits the act/grad scratch, activations, two grad buffers, 2*P age ints
-// when partitioned. The partition tables are read when part only.
+// bytes of LDS of tick_mlp_comp_kernel: W, +W2 unless MERGE_UPDATE, +the
+// sampled pre-merge copy unless it fits the act/grad scratch (*w3_alias),
+// activations, two grad buffers, 2*P age ints when partitioned (P > 0)
+static size_t mlp_comp_lds_bytes(bool part, int64_t D, size_t scratch,
+                                 int64_t mode, int64_t P, int* w3_alias)
+{
+    size_t w_slabs = (mode == MODE_MERGE_UPDATE) ? 1 : 2;
+    *w3_alias = (!part && scratch >= (size_t)D) ? 1 : 0;
+    if (!part && !*w3_alias) w_slabs += 1;
+    return sizeof(float) * (w_slabs * (size_t)D + scratch) +
+           sizeof(int) * 2 * (size_t)P;
+}
+
+// Which kernel serves a compressed MLP tick whose LDS-resident plan needs
+// `smem` bytes: tick_mlp_comp_kernel, unless GOSSIPY_MLP_COMP_WIDE=1 selects
+// tick_mlp_comp_wide_kernel on any shape. The wide kernel is opt-in: unset or
+// 0, a shape past the budget raises the budget error.
+static bool mlp_comp_use_wide(const char* what, size_t smem)
+{
+    const char* v = getenv("GOSSIPY_MLP_COMP_WIDE");
+    if (v && *v && atoi(v) != 0) return true;
+    TORCH_CHECK(smem <= LDS_BUDGET, what, " mlp LDS budget exceeded (", smem,
+                " B > 163840 B); shrink batch_size/hidden, or use"
+                " MERGE_UPDATE (the other modes hold a second model slab)."
+                " The global-resident wide kernel covers the plain MLP tick"
+                " only; GOSSIPY_MLP_COMP_WIDE=1 selects"
+                " tick_mlp_comp_wide_kernel, which keeps the rows in device"
+                " memory");
+    return false;
+}
+
+// bytes of LDS tick_mlp_comp_wide_kernel holds on any shape: two age vectors
+// of P ints (partitioned, P > 0) or the bitmap of ceil(D/32) words (sampled)
+static size_t mlp_comp_wide_fixed(const char* what, int64_t P, int64_t D)
+{
+    size_t fixed = P > 0 ? sizeof(int) * 2 * (size_t)P
+                         : sizeof(unsigned) * (((size_t)D + 31) / 32);
+    TORCH_CHECK(fixed <= LDS_BUDGET, what, " mlp wide LDS budget exceeded: ",
+                P > 0 ? "the two age vectors of n_parts ints"
+                      : "the bitmap of one bit per parameter",
+                " alone take ", fixed, " B > 163840 B");
+    return fixed;
+}
+
+// Partitioned (part) or sampled compressed MLP: tick_mlp_comp_kernel within
+// its per-mode LDS budget (mlp_comp_lds_bytes), or the wide kernel under its
+// knob (mlp_comp_use_wide). The partition tables are read when part only.
 static Plan<MlpCompArgs> mlp_comp_plan(
     bool part, const StateTensors& st, torch::Tensor layout, int64_t n_layers,
     torch::Tensor perm, torch::Tensor pptr, torch::Tensor apart,
@@ -4796,23 +5025,68 @@ static Plan<MlpCompArgs> mlp_comp_plan(
     } else {
         TORCH_CHECK(samp_c >= 1, "samp_c must be positive");
     }
-    size_t w_slabs = (mode == MODE_MERGE_UPDATE) ? 1 : 2;
-    if (!part) {
-        c.w3_alias = (g.scratch >= (size_t)a.D) ? 1 : 0;
-        if (!c.w3_alias) w_slabs += 1;
-    }
-    L.smem = sizeof(float) * (w_slabs * (size_t)a.D + g.scratch) +
-             sizeof(int) * 2 * (size_t)c.P;
-    TORCH_CHECK(L.smem <= 160 * 1024, what, " mlp LDS budget exceeded (",
-                L.smem, " B > 163840 B); shrink batch_size/hidden, or use"
-                " MERGE_UPDATE (the other modes hold a second model slab)."
-                " The global-resident wide kernel covers the plain MLP tick"
-                " only");
-    L.kernel = part ? tick_mlp_comp_kernel<true> : tick_mlp_comp_kernel<false>;
+    L.smem = mlp_comp_lds_bytes(part, a.D, g.scratch, mode, c.P, &c.w3_alias);
     L.threads = g.threads;
     // snapshots copy one age per partition
     L.snap = {a.D, a.D, 0, part ? (int)n_parts : 1};
+    if (!mlp_comp_use_wide(what, L.smem)) {
+        L.kernel = part ? tick_mlp_comp_kernel<true>
+                        : tick_mlp_comp_kernel<false>;
+        return L;
+    }
+    // wide: act / grad join the age vectors or the bitmap in LDS when the
+    // sum fits, else they follow W2 in the workspace row. One row per node
+    // bounds every launch, as receivers are unique within one.
+    a.act_max = g.out_max;
+    size_t fixed = mlp_comp_wide_fixed(what, c.P, a.D);
+    bool act_ws = sizeof(float) * g.wide_scratch + fixed > LDS_BUDGET;
+    L.smem = (act_ws ? 0 : sizeof(float) * g.wide_scratch) + fixed;
+    a.ws_row = (mode != MODE_MERGE_UPDATE ? a.D : 0) +
+               (act_ws ? (long)g.wide_scratch : 0);
+    size_t ws_bytes = sizeof(float) * (size_t)a.ws_row * st.params.size(0);
+    TORCH_CHECK(ws_bytes <= ((size_t)1 << 34),
+        what, " mlp wide workspace too large: ", st.params.size(0),
+        " nodes x ", a.ws_row, " floats (trained copy of the received model +"
+        " a batch's activations and gradients) = ", ws_bytes,
+        " B > 16 GiB; shrink batch_size/hidden");
+    a.ws = a.ws_row ? mlp_wide_workspace(st.params.device(),
+                                         (size_t)a.ws_row * st.params.size(0))
+                    : nullptr;
+    if (part)
+        L.kernel = act_ws ? tick_mlp_comp_wide_kernel<true, true>
+                          : tick_mlp_comp_wide_kernel<true, false>;
+    else
+        L.kernel = act_ws ? tick_mlp_comp_wide_kernel<false, true>
+                          : tick_mlp_comp_wide_kernel<false, false>;
     return L;
+}
+
+// "lds" or "wide": the kernel mlp_comp_plan picks for a partitioned
+// (n_parts > 0) or sampled (samp_c > 0) MLP tick of layer widths `dims` on
+// shards of stride Smax; raises the plan's budget errors
+static std::string mlp_comp_tick_path(std::vector<int64_t> dims, int64_t bs,
+                                      int64_t Smax, int64_t mode,
+                                      int64_t n_parts, int64_t samp_c)
+{
+    TORCH_CHECK(dims.size() >= 2, "dims must hold d_in and n_classes");
+    TORCH_CHECK((n_parts > 0) != (samp_c > 0),
+                "one of n_parts and samp_c must be positive");
+    bool part = n_parts > 0;
+    const char* what = part ? "partitioned" : "sampled";
+    int64_t D = 0, out_sum = 0, width_max = dims[0];
+    for (size_t l = 0; l + 1 < dims.size(); ++l) {
+        D += dims[l + 1] * dims[l] + dims[l + 1];
+        out_sum += dims[l + 1];
+        width_max = std::max(width_max, dims[l + 1]);
+    }
+    int alias;
+    size_t lds = mlp_comp_lds_bytes(
+        part, D, mlp_scratch(batch_rows(bs, (int)Smax), dims[0], out_sum,
+                             width_max, false),
+        mode, part ? n_parts : 0, &alias);
+    if (!mlp_comp_use_wide(what, lds)) return "lds";
+    mlp_comp_wide_fixed(what, part ? n_parts : 0, D);
+    return "wide";
 }
 
 // ---------------------------------------------------------------------------
@@ -4839,6 +5113,14 @@ static void launch_tick(Plan<Args>& L, const TickEvents& ev, bool update_only,
     if (chan) L.a.*chan = iptr(chan_vals);
     launch_kernel(plan_kernel(L, n), n, L.threads, L.smem, current_stream(),
                   L.a);
+}
+
+// The receivers of an MLP launch are unique: the wide kernels work on the
+// params rows in place, and their workspace has one row per node.
+static void check_receivers(const char* who, int64_t n, int64_t n_nodes)
+{
+    TORCH_CHECK(n <= n_nodes, who, ": a launch of ", n, " receivers for ",
+                n_nodes, " nodes");
 }
 
 // `merge_limit` of the logreg and MLP entry points is the limited-merge
@@ -4880,10 +5162,7 @@ void tick_mlp(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
 {
     auto L = mlp_plan({params, ages, slots, slot_ages, X, Y, counts},
                       layout, n_layers, lr, wd, epochs, bs, mode, merge_limit);
-    // receivers are unique within a launch (the wide kernel's workspace has
-    // one row per node)
-    TORCH_CHECK(nodes.size(0) <= params.size(0), "tick_mlp: ", nodes.size(0),
-                " receivers for ", params.size(0), " nodes");
+    check_receivers("tick_mlp", nodes.size(0), params.size(0));
     launch_tick(L, {nodes, recv_ptr, del_slots, reply_slots}, update_only,
                 &MlpArgs::dmodes, dmodes);
 }
@@ -4931,6 +5210,7 @@ void tick_mlp_part(
     auto L = mlp_comp_plan(true, {params, ages, slots, slot_ages, X, Y, counts},
                            layout, n_layers, perm, pptr, apart, n_parts, 0,
                            lr, wd, epochs, bs, mode);
+    check_receivers("tick_mlp_part", nodes.size(0), params.size(0));
     launch_tick(L, {nodes, recv_ptr, del_slots, reply_slots}, update_only,
                 &MlpCompArgs::dpids, del_pids);
 }
@@ -4947,6 +5227,7 @@ void tick_mlp_samp(
     auto L = mlp_comp_plan(false, {params, ages, slots, slot_ages, X, Y, counts},
                            layout, n_layers, {}, {}, {}, 0, samp_c,
                            lr, wd, epochs, bs, mode);
+    check_receivers("tick_mlp_samp", nodes.size(0), params.size(0));
     launch_tick(L, {nodes, recv_ptr, del_slots, reply_slots}, update_only,
                 &MlpCompArgs::dpids, del_seeds);
 }
@@ -5240,19 +5521,20 @@ static void run_round_logreg_samp(
     stream_round(L, c.r, &LogregSampArgs::dseeds);
 }
 
+static void check_round_receivers(const char* who, const RoundCall& c)
+{
+    for (int t = 0; t < c.r.delta; ++t)
+        for (const int* p : {c.r.tptr[RT_RECV], c.r.tptr[RT_REP]})
+            check_receivers(who, p[t + 1] - p[t], c.st.params.size(0));
+}
+
 static void run_round_mlp(
     const RoundCall& c, torch::Tensor layout, int64_t n_layers, double lr,
     double wd, int64_t epochs, int64_t bs, int64_t mode, int64_t merge_limit)
 {
     auto L = mlp_plan(c.st, layout, n_layers, lr, wd, epochs, bs, mode,
                       merge_limit);
-    // receivers are unique within a launch (the wide kernel's workspace has
-    // one row per node)
-    for (int t = 0; t < c.r.delta; ++t)
-        for (const int* p : {c.r.tptr[RT_RECV], c.r.tptr[RT_REP]})
-            TORCH_CHECK(p[t + 1] - p[t] <= c.st.params.size(0),
-                        "run_round_mlp: a launch of ", p[t + 1] - p[t],
-                        " receivers for ", c.st.params.size(0), " nodes");
+    check_round_receivers("run_round_mlp", c);
     stream_round(L, c.r);
 }
 
@@ -5264,6 +5546,7 @@ static void run_round_mlp_part(
 {
     auto L = mlp_comp_plan(true, c.st, layout, n_layers, perm, pptr, apart,
                            n_parts, 0, lr, wd, epochs, bs, mode);
+    check_round_receivers("run_round_mlp_part", c);
     stream_round(L, c.r, &MlpCompArgs::dpids);
 }
 
@@ -5274,6 +5557,7 @@ static void run_round_mlp_samp(
 {
     auto L = mlp_comp_plan(false, c.st, layout, n_layers, {}, {}, {}, 0,
                            samp_c, lr, wd, epochs, bs, mode);
+    check_round_receivers("run_round_mlp_samp", c);
     stream_round(L, c.r, &MlpCompArgs::dpids);
 }
 
@@ -6479,6 +6763,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           "fused partition-merge + age-rescaled MLP SGD tick");
     m.def("tick_mlp_samp", &tick_mlp_samp,
           "fused sampled-merge + MLP SGD tick");
+    m.def("mlp_comp_tick_path", &mlp_comp_tick_path,
+          "\"lds\" or \"wide\": the kernel tick_mlp_part / tick_mlp_samp and"
+          " their whole-round executors run for (dims, bs, Smax, mode,"
+          " n_parts, samp_c)");
     m.def("run_round_mlp_part", round_entry(run_round_mlp_part),
           "whole-round executor, partitioned MLP family",
           py::call_guard<py::gil_scoped_release>());
