@@ -31,6 +31,10 @@ def main():
     ap.add_argument("--rounds", type=int, default=50)
     ap.add_argument("--k", type=int, default=4)
     ap.add_argument("--dim", type=int, default=16)
+    ap.add_argument("--matching", choices=["naive", "hungarian"],
+                    default="naive",
+                    help="centroid merge: plain mean, or the mean of the"
+                         " minimum-cost matched centroids")
     args = ap.parse_args()
 
     device = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
@@ -59,9 +63,16 @@ def main():
         seed=42,
     )
     spec = KMeansSpec(
-        k=args.k, dim=args.dim, alpha=0.1, mode=CreateModelMode.MERGE_UPDATE
+        k=args.k, dim=args.dim, alpha=0.1, mode=CreateModelMode.MERGE_UPDATE,
+        matching=args.matching,
     )
     sim = BatchedGossipSimulator(cfg, spec, data, device=device)
+    if args.matching == "hungarian":
+        # "kernel" (tick_kmeans_match_kernel, GOSSIPY_KMEANS_MATCH_KERNEL=1)
+        # or "host" (device cdist + scipy per delivery wave)
+        path = (sim.backend.kmeans_match_path(spec, data)
+                if sim.backend.name == "hip" else "torch")
+        print(f"hungarian merge path:    {path}")
     report = SimulationReport()
     sim.add_receiver(report)
     sim.init_nodes()

@@ -70,6 +70,21 @@ _MODE_ID = {
     CreateModelMode.PASS: 3,
 }
 
+#: routes hungarian k-means deliveries, see HIPBackend.kmeans_match_path
+_KMEANS_MATCH_KNOB = "GOSSIPY_KMEANS_MATCH_KERNEL"
+
+
+def _env_knob(name: str) -> int:
+    """1, 0, or -1 when unset or empty: an on/off environment knob, read the
+    way the extension reads its own (``atoi``: text that is no number is 0)."""
+    v = os.environ.get(name, "")
+    if not v:
+        return -1
+    try:
+        return int(int(v) != 0)
+    except ValueError:
+        return 0
+
 
 def metric_rows_to_dicts(rows) -> list:
     """Metric dicts from the eval kernel's ``[R, 5]`` rows (accuracy,
@@ -1365,6 +1380,18 @@ class HIPBackend(TorchBackend):
             spec.family == "kmeans"
             and getattr(spec, "matching", "naive") == "hungarian"
         ):
+            if self.kmeans_match_path(spec, data) == "kernel":
+                dev = state.params.device
+                self.ext.tick_kmeans_match(
+                    state.params, state.ages, pool.slots, pool.slot_ages,
+                    recv_nodes.to(dev, torch.int32),
+                    recv_ptr.to(dev, torch.int32),
+                    del_slots.to(dev, torch.int32),
+                    reply_slots.to(dev, torch.int32),
+                    data.x, data.counts, spec.k, spec.dim, spec.alpha,
+                    _MODE_ID[spec.mode], False,
+                )
+                return
             self._deliver_kmeans_hungarian(
                 state, pool, data, spec, recv_nodes, recv_ptr, del_slots,
                 reply_slots,
@@ -1411,6 +1438,8 @@ class HIPBackend(TorchBackend):
         ):
             raise ValueError(
                 f"hungarian kmeans engine path: mode {mode} unsupported"
+                f" on the host route; tick_kmeans_match_kernel serves it"
+                f" for k <= 64 unless {_KMEANS_MATCH_KNOB}=0"
             )
         dev = state.params.device
         ptr = recv_ptr.long()
@@ -1983,6 +2012,33 @@ class HIPBackend(TorchBackend):
         return self.ext.pens_tick_path(
             spec.d_in, spec.n_classes, spec.batch_size, data.x.shape[1],
         )
+
+    def kmeans_match_path(self, spec, data) -> str:
+        """Which code delivers to a ``KMeansSpec(matching="hungarian")`` on
+        the shards of ``data``: ``"kernel"`` (``tick_kmeans_match_kernel``:
+        cost block, assignment and matched mean of every delivery in the one
+        launch per tick) or ``"host"`` (``_deliver_kmeans_hungarian``: per
+        delivery wave a device cdist, scipy's assignment on the host and the
+        update kernel). With ``GOSSIPY_KMEANS_MATCH_KERNEL`` unset,
+        MERGE_UPDATE, UPDATE and PASS take the host route and UPDATE_MERGE,
+        which the host route does not implement, the kernel; ``=1`` sends
+        every mode to the kernel; ``=0`` keeps the kernel off. The kernel
+        takes ``k <= 64`` within the 160 KB of LDS; a shape past that keeps
+        the host route. An UPDATE_MERGE delivery raises on the host route."""
+        if spec.family != "kmeans" or spec.matching != "hungarian":
+            raise ValueError(
+                'kmeans_match_path: a KMeansSpec(matching="hungarian") is'
+                " required"
+            )
+        knob = _env_knob(_KMEANS_MATCH_KNOB)
+        wanted = knob == 1 or (
+            knob == -1 and spec.mode == CreateModelMode.UPDATE_MERGE
+        )
+        if wanted and self.ext.kmeans_match_fits(
+            spec.k, spec.dim, data.x.shape[1]
+        ):
+            return "kernel"
+        return "host"
 
     def _family_call(self, spec, dev):
         """The one mapping from a spec to extension arguments. Returns

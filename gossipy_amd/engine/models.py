@@ -401,10 +401,21 @@ class KMeansSpec:
     ``matching="hungarian"`` (bug-fixed column-index matching, see
     gossipy_amd/model/handler.py — the reference's own hungarian path is
     a no-op identity permutation, handler.py:629-630) runs on BOTH
-    backends: the torch loop, and on the engine a wave-batched device
-    cdist + host assignment + batched matched-mean feeding the HIP EMA
-    update (HIPBackend._deliver_kmeans_hungarian). ``naive`` is the
-    behavior the reference actually ships and stays fully in-kernel.
+    backends: the torch loop, and on the engine one of two routes that
+    ``HIPBackend.kmeans_match_path`` names. ``"host"``: a wave-batched
+    device cdist + host assignment + batched matched-mean feeding the HIP
+    EMA update (HIPBackend._deliver_kmeans_hungarian); MERGE_UPDATE, UPDATE
+    and PASS only. ``"kernel"``: ``tick_kmeans_match_kernel``, one launch
+    per tick with the cost block, a shortest-augmenting-path assignment on
+    one wave and the matched mean in LDS; all four modes, ``k <= 64``.
+    With ``GOSSIPY_KMEANS_MATCH_KERNEL`` unset the kernel serves
+    UPDATE_MERGE and the host route the rest; ``=1`` sends every mode to
+    the kernel, ``=0`` none (UPDATE_MERGE then raises). Tie rule: among
+    assignments of exactly equal total cost the kernel takes the column of
+    lowest index at each arg-min, which need not be scipy's choice;
+    duplicate centroids are the only realistic source of such ties.
+    ``naive`` is the behavior the reference actually ships and stays fully
+    in-kernel.
     """
 
     k: int

@@ -1441,6 +1441,184 @@ tick_kmeans_kernel(KMeansArgs a)
 }
 
 // ---------------------------------------------------------------------------
+// k-means tick with Hungarian-matched merges (K12, matching="hungarian")
+//
+// tick_kmeans_kernel with the plain mean of MERGE_UPDATE / UPDATE_MERGE
+// replaced by C[i] = 0.5f * (C[i] + O[perm[i]]), perm the minimum-cost
+// assignment of cost[i][j] = ||C_i - O_j||_2 (rows: own centroids, columns:
+// received ones) -- what TorchBackend._merge_kmeans computes with scipy.
+// Three phases per merge share the dynamic LDS:
+//   1. cost block: all threads over (i, j) pairs, direct differences (the
+//      |c|^2 + |o|^2 - 2 c.o expansion cancels and can reorder near-equal
+//      costs), sqrtf, into a k x k LDS block;
+//   2. assignment: shortest augmenting paths with potentials, wave 0 alone,
+//      lane j owning column j (hence k <= 64), everything in registers;
+//   3. matched mean: all threads, through perm in LDS.
+// Every loop has a static trip bound, NaN costs included.
+// ---------------------------------------------------------------------------
+
+// a value every lane of the wave holds, moved to a scalar register
+DEV_INLINE int wave_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+
+// Phase 2, run by the 64 lanes of wave 0. Lane j holds the dual v[j], the
+// slack minv[j], the tree edge way[j], used[j] and the matched row p[j] of
+// column j; lane r also holds the dual u[r] of row r and whether row r is in
+// the alternating tree. Row i is inserted by at most i + 1 scan steps: every
+// step marks one more column used, only the i matched columns can be passed,
+// and the arg-min below always returns an unused column. The path flip
+// follows way[], which points from a column to one used earlier, so it ends
+// within k steps as well.
+DEV_INLINE void kmeans_assign_wave(const float* cost, int k, int* perm)
+{
+    const int lane = threadIdx.x;
+    const float INF = __builtin_huge_valf();
+    float u = 0.f, v = 0.f;
+    int p = -1;
+    for (int i = 0; i < k; ++i) {
+        float minv = INF;
+        int way = -1;  // -1: the root, row i itself
+        bool used = false, rowin = lane == i;
+        int i0 = i, j0 = -1;
+        for (int step = 0; step < k; ++step) {
+            float ui0 = __shfl(u, i0, WAVE);
+            bool cand = lane < k && !used;
+            if (cand) {
+                float cur = cost[i0 * k + lane] - ui0 - v;
+                if (cur < minv) { minv = cur; way = j0; }
+            }
+            // arg-min of (minv, column) over the unused columns. NaN counts
+            // as +inf and used / idle lanes sort behind every column, so the
+            // keys are totally ordered: all lanes agree, the lowest column
+            // wins on equal values, and with nothing but inf left the lowest
+            // unused column comes out.
+            float bv = (cand && minv == minv) ? minv : INF;
+            int bj = cand ? lane : WAVE + lane;
+            for (int off = WAVE / 2; off > 0; off >>= 1) {
+                float ov = __shfl_xor(bv, off, WAVE);
+                int oj = __shfl_xor(bj, off, WAVE);
+                if (ov < bv || (ov == bv && oj < bj)) { bv = ov; bj = oj; }
+            }
+            int j1 = wave_uniform(bj) & (WAVE - 1);
+            float delta = __shfl(bv, 0, WAVE);
+            if (rowin) u += delta;
+            if (used) v -= delta; else minv -= delta;
+            j0 = j1;
+            int pj = wave_uniform(__shfl(p, j1, WAVE));
+            if (pj < 0) break;  // a free column: the path is complete
+            i0 = pj;
+            if (lane == j1) used = true;
+            if (lane == i0) rowin = true;
+        }
+        // flip the path from the free column back to the root
+        int j = j0;
+        for (int t = 0; t < k; ++t) {
+            int w = wave_uniform(__shfl(way, j, WAVE));
+            int pw = w >= 0 ? wave_uniform(__shfl(p, w, WAVE)) : i;
+            if (lane == j) p = pw;
+            if (w < 0) break;
+            j = w;
+        }
+    }
+    if (lane < k && (unsigned)p < (unsigned)k) perm[p] = lane;
+}
+
+// C[i] = 0.5f * (C[i] + O[perm[i]]) for the two k x dim slabs C and O in LDS.
+// Lanes run along j, so the reads of O are dim floats apart: 32 lanes on one
+// bank when dim % 32 == 0. Each lane therefore starts its sum over e at
+// e = j % dim (a per-lane skew); both slabs keep the dense layout
+// kmeans_update reads.
+DEV_INLINE void kmeans_matched_mean(const KMeansArgs& a, float* C,
+                                    const float* O, float* cost, int* perm)
+{
+    const int tid = threadIdx.x, k = a.k, dim = a.dim;
+    for (int q = tid; q < k * k; q += blockDim.x) {
+        int i = q / k, j = q - i * k;
+        const float* ci = C + i * dim;
+        const float* oj = O + j * dim;
+        int e = j % dim;
+        float s = 0.f;
+        for (int n = 0; n < dim; ++n) {
+            float t = ci[e] - oj[e];
+            s += t * t;
+            if (++e == dim) e = 0;
+        }
+        cost[q] = sqrtf(s);
+    }
+    for (int i = tid; i < k; i += blockDim.x) perm[i] = i;
+    __syncthreads();
+    if (tid < WAVE) kmeans_assign_wave(cost, k, perm);
+    __syncthreads();
+    for (int e = tid; e < a.D; e += blockDim.x) {
+        int i = e / dim;
+        C[e] = 0.5f * (C[e] + O[perm[i] * dim + (e - i * dim)]);
+    }
+    __syncthreads();
+}
+
+__global__ void __launch_bounds__(128)
+tick_kmeans_match_kernel(KMeansArgs a)
+{
+    int i = blockIdx.x;
+    int node = a.nodes[i];
+    int tid = threadIdx.x;
+    extern __shared__ float sm[];
+    float* C = sm;                       // D = k*dim
+    float* C2 = C + a.D;                 // received model (trained copy in
+                                         // UPDATE_MERGE)
+    int* assign = (int*)(C2 + a.D);      // Smax
+    float* cost = (float*)(assign + a.Smax);  // k*k
+    int* perm = (int*)(cost + a.k * a.k);     // k
+
+    for (int e = tid; e < a.D; e += blockDim.x)
+        C[e] = a.params[(long)node * a.D + e];
+    __syncthreads();
+    int age = a.ages[node];
+
+    if (a.update_only) {
+        kmeans_update(a, node, C, assign, age);
+    } else {
+        for (int j = a.ptr[i]; j < a.ptr[i + 1]; ++j) {
+            int slot = a.dslots[j];
+            const float* srow = a.slots + (long)slot * a.D;
+            int sage = a.slot_ages[slot];
+            if (a.mode == MODE_MERGE_UPDATE) {
+                for (int e = tid; e < a.D; e += blockDim.x) C2[e] = srow[e];
+                __syncthreads();
+                kmeans_matched_mean(a, C, C2, cost, perm);
+                kmeans_update(a, node, C, assign, age);
+            } else if (a.mode == MODE_UPDATE) {
+                for (int e = tid; e < a.D; e += blockDim.x) C[e] = srow[e];
+                age = sage;
+                __syncthreads();
+                kmeans_update(a, node, C, assign, age);
+            } else if (a.mode == MODE_UPDATE_MERGE) {
+                kmeans_update(a, node, C, assign, age);
+                for (int e = tid; e < a.D; e += blockDim.x) C2[e] = srow[e];
+                __syncthreads();
+                int age2 = sage;
+                kmeans_update(a, node, C2, assign, age2);
+                kmeans_matched_mean(a, C, C2, cost, perm);
+            } else {  // PASS
+                for (int e = tid; e < a.D; e += blockDim.x) C[e] = srow[e];
+                age = sage;
+                __syncthreads();
+            }
+            int rs = a.rslots ? a.rslots[j] : -1;
+            if (rs >= 0) {
+                for (int e = tid; e < a.D; e += blockDim.x)
+                    a.slots[(long)rs * a.D + e] = C[e];
+                if (tid == 0) a.slot_ages[rs] = age;
+                __syncthreads();
+            }
+        }
+    }
+    __syncthreads();
+    for (int e = tid; e < a.D; e += blockDim.x)
+        a.params[(long)node * a.D + e] = C[e];
+    if (tid == 0) a.ages[node] = age;
+}
+
+// ---------------------------------------------------------------------------
 // pegasos / adaline tick: one WAVE per node, weights in registers
 // ---------------------------------------------------------------------------
 
@@ -4781,6 +4959,51 @@ static Plan<KMeansArgs> kmeans_plan(const StateTensors& st, int64_t k,
     return L;
 }
 
+// bytes of dynamic LDS tick_kmeans_match_kernel needs: the two centroid
+// slabs and the assign[] of the naive kernel, the k x k cost block and perm[]
+// (the duals of the assignment live in wave 0's registers)
+static size_t kmeans_match_lds_bytes(int64_t k, int64_t dim, int64_t Smax)
+{
+    return sizeof(float) * (size_t)(2 * k * dim + k * k) +
+           sizeof(int) * (size_t)(Smax + k);
+}
+
+// whether tick_kmeans_match_kernel takes (k, dim) on shards of stride Smax:
+// one lane per column, and the LDS plan within the budget
+static bool kmeans_match_fits(int64_t k, int64_t dim, int64_t Smax)
+{
+    return k >= 1 && k <= WAVE && dim >= 1 && Smax >= 0 &&
+           kmeans_match_lds_bytes(k, dim, Smax) <= 160 * 1024;
+}
+
+static Plan<KMeansArgs> kmeans_match_plan(const StateTensors& st, int64_t k,
+                                          int64_t dim, double alpha,
+                                          int64_t mode)
+{
+    Plan<KMeansArgs> L;
+    KMeansArgs& a = L.a;
+    fill_state_x(a, st);
+    TORCH_CHECK(k >= 1 && k <= WAVE && dim >= 1,
+                "kmeans matched merge: k = ", k, ", dim = ", dim,
+                " unsupported (one lane per centroid: 1 <= k <= ", WAVE, ")");
+    TORCH_CHECK(st.params.size(1) == k * dim && st.slots.size(1) == k * dim &&
+                    st.X.dim() == 3 && st.X.size(2) == dim,
+                "kmeans matched merge: rows of k * dim = ", k * dim,
+                " floats and samples of dim = ", dim, " expected");
+    TORCH_CHECK(mode >= MODE_UPDATE && mode <= MODE_PASS, "mode ", mode,
+                " unknown");
+    a.k = k; a.dim = dim; a.D = k * dim;
+    a.alpha = alpha; a.mode = mode;
+    L.smem = kmeans_match_lds_bytes(k, dim, a.Smax);
+    TORCH_CHECK(L.smem <= 160 * 1024,
+                "kmeans matched merge LDS budget exceeded: k = ", k,
+                ", dim = ", dim, " need ", L.smem, " bytes");
+    L.kernel = tick_kmeans_match_kernel;
+    L.threads = 128;
+    L.snap = {a.D, a.D, 0, 1};
+    return L;
+}
+
 // What the plain and the compressed MLP plan share: state, layout and SGD
 // fields of the MlpArgs, and the launch geometry the layer shapes imply.
 struct MlpGeom {
@@ -5253,6 +5476,21 @@ void tick_kmeans(torch::Tensor params, torch::Tensor ages, torch::Tensor slots,
 {
     auto L = kmeans_plan({params, ages, slots, slot_ages, X, {}, counts},
                          k, dim, alpha, mode);
+    launch_tick(L, {nodes, recv_ptr, del_slots, reply_slots}, update_only);
+}
+
+// tick_kmeans with the Hungarian-matched mean in MERGE_UPDATE / UPDATE_MERGE
+void tick_kmeans_match(torch::Tensor params, torch::Tensor ages,
+                       torch::Tensor slots, torch::Tensor slot_ages,
+                       torch::Tensor nodes, torch::Tensor recv_ptr,
+                       torch::Tensor del_slots, torch::Tensor reply_slots,
+                       torch::Tensor X, torch::Tensor counts, int64_t k,
+                       int64_t dim, double alpha, int64_t mode,
+                       bool update_only)
+{
+    auto L = kmeans_match_plan({params, ages, slots, slot_ages, X, {}, counts},
+                               k, dim, alpha, mode);
+    check_receivers("tick_kmeans_match", nodes.size(0), params.size(0));
     launch_tick(L, {nodes, recv_ptr, del_slots, reply_slots}, update_only);
 }
 
@@ -6811,4 +7049,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           "whether eval_mlp_wide takes an MLP of (dims, n_eval)");
     m.def("tick_kmeans", &tick_kmeans,
           "fused centroid merge + assign/EMA k-means tick (K11)");
+    m.def("tick_kmeans_match", &tick_kmeans_match,
+          "tick_kmeans with the Hungarian-matched mean (K12): cost block,"
+          " assignment and matched mean in the one launch; k <= 64");
+    m.def("kmeans_match_fits", &kmeans_match_fits,
+          "whether tick_kmeans_match takes (k, dim, Smax); host code, no GPU"
+          " needed");
 }
