@@ -17,6 +17,10 @@ from there on the step-1 event misses the LDS plan of ``tick_pens_kernel``
 (``4 * (D + rows * 784 + rows * 10)`` bytes; 32 rows still fit) and runs
 ``tick_pens_wide_kernel``, which scores all candidates in one MFMA GEMM. The
 script then prints the PENS event path as well.
+
+``--eval-rank`` sets ``GOSSIPY_EVAL_RANK=1``: the shared eval set is measured
+by the chunk-sorted kernels (``eval_metrics_rank``), which take any number of
+rows; the script prints the evaluation path either way.
 """
 
 import os
@@ -52,9 +56,14 @@ def main():
     ap.add_argument("--mode", choices=sorted(MODES), default="merge_update")
     ap.add_argument("--pens", action="store_true",
                     help="PENS neighbour selection (MERGE_UPDATE only)")
+    ap.add_argument("--eval-rank", action="store_true",
+                    help="chunk-sorted evaluation kernels at any eval-set"
+                         " size (sets GOSSIPY_EVAL_RANK=1)")
     args = ap.parse_args()
     if args.batch_size is None:
         args.batch_size = 64 if args.pens else 32
+    if args.eval_rank:
+        os.environ["GOSSIPY_EVAL_RANK"] = "1"
 
     device = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
     n, d, k = args.nodes, 784, 10
@@ -91,6 +100,10 @@ def main():
     if args.pens:
         path = sim.backend.pens_tick_path(spec, data) if hip else "torch (no GPU)"
         print(f"pens_tick_path {path}")
+    if hip:
+        n_eval = data.gx.shape[0]
+        print(f"eval_metrics_path ({n_eval} rows)"
+              f" {sim.backend.eval_metrics_path(spec, n_eval)}")
     report = SimulationReport()
     sim.add_receiver(report)
     sim.init_nodes()

@@ -1754,6 +1754,59 @@ class HIPBackend(TorchBackend):
         graph.replay()
         return out_static
 
+    def eval_metrics_path(self, spec, n_eval):
+        """The route of a shared-set evaluation of ``spec`` on ``n_eval``
+        rows, the one condition :meth:`eval_metrics_fast` and
+        :meth:`eval_metrics_launch` share:
+
+        * ``"pairwise"``: ``eval_metrics`` / ``eval_metrics_scores``, one
+          block per model with the whole set in LDS and the pairwise
+          Mann-Whitney loop; at most 2048 rows.
+        * ``"rank"``: ``eval_metrics_rank`` / ``eval_metrics_rank_scores``,
+          chunks of ``ext.EVAL_RANK_CH`` rows, per chunk a sorted run of the
+          negatives' score keys, binary-search ranks of the positives and a
+          64-bit integer win count: exact at any ``n_eval``. Taken at every
+          size under ``GOSSIPY_EVAL_RANK=1``, never otherwise.
+        * ``"torch"``: torch scores and the tensor metrics chain
+          (:meth:`_eval_metrics_torch`; ``eval_metrics_fast`` returns
+          ``None``), past 2048 rows without the knob.
+
+        ``None`` for a family on the generic path."""
+        if spec.family not in ("logreg", "pegasos", "adaline", "mlp",
+                               "torchmod"):
+            return None
+        if os.environ.get("GOSSIPY_EVAL_RANK", "0") not in ("", "0"):
+            return "rank"
+        # blocks run concurrently, so the pairwise kernel's wall time tracks
+        # the PER-BLOCK pairwise-AUC work (~n_eval^2): n_eval <= 2048 keeps
+        # a block under ~100 us at any sampled-node count (2300 samples was
+        # 58% of the 50k-node round)
+        return "pairwise" if n_eval <= 2048 else "torch"
+
+    def _eval_metrics_hip(self, path, state, spec, local_ids, gx, gy):
+        """``[R, 5]`` device metrics of the ``"pairwise"`` or ``"rank"``
+        route. Affine/margin families score inside the kernel; MLP/torchmod
+        run their (batched) forward first and feed the scores in."""
+        rank = path == "rank"
+        if spec.family in ("logreg", "pegasos", "adaline"):
+            is_margin = spec.family in ("pegasos", "adaline")
+            args = (
+                state.params,
+                local_ids.to(state.params.device, torch.int32),
+                gx,
+                gy,
+                spec.d_in,
+                1 if is_margin else spec.n_classes,
+                is_margin,
+            )
+            if rank:
+                return self.ext.eval_metrics_rank(*args)
+            return self.ext.eval_metrics(*args, _EMPTY_I32)
+        sc = self.scores(state, spec, local_ids, gx)
+        fn = (self.ext.eval_metrics_rank_scores if rank
+              else self.ext.eval_metrics_scores)
+        return fn(sc.contiguous(), gy, sc.shape[-1], False)
+
     def eval_metrics_launch(self, state, spec, local_ids, gx, gy):
         """Asynchronous half of :meth:`eval_metrics_fast`: enqueue the K13
         kernel and a non-blocking D2H into a pinned staging buffer, record
@@ -1764,38 +1817,15 @@ class HIPBackend(TorchBackend):
         MLP/torchmod run their (batched) forward first and feed the
         precomputed scores to the same metrics epilogue (``eval_mlp_wide``
         has a shared-set mode, which measured slower than this at
-        784-100-10, profiles/mlp_wide_eval.md, and is not wired in). Returns
+        784-100-10, profiles/mlp_wide_eval.md, and is not wired in).
+        :meth:`eval_metrics_path` names the route: past 2048 rows the torch
+        chain, or under ``GOSSIPY_EVAL_RANK=1`` the chunk-sorted kernels at
+        every size; each result rides the same pinned staging. Returns
         ``None`` for unsupported families."""
-        if (
-            spec.family in ("logreg", "pegasos", "adaline")
-            and gx.shape[0] <= 2048
-        ):
-            # blocks run concurrently, so the kernel's wall time tracks the
-            # PER-BLOCK pairwise-AUC work (~n_eval^2): n_eval <= 2048 keeps
-            # a block under ~100 us at any sampled-node count. Bigger eval
-            # sets (2300 samples was 58% of the 50k-node round) take the
-            # torch O(n log n) sort path
-            is_margin = spec.family in ("pegasos", "adaline")
-            out = self.ext.eval_metrics(
-                state.params,
-                local_ids.to(state.params.device, torch.int32),
-                gx,
-                gy,
-                spec.d_in,
-                1 if is_margin else spec.n_classes,
-                is_margin,
-                _EMPTY_I32,
-            )
-        elif (
-            spec.family in ("mlp", "torchmod")
-            and gx.shape[0] <= 2048
-        ):
-            sc = self.scores(state, spec, local_ids, gx)
-            out = self.ext.eval_metrics_scores(
-                sc.contiguous(), gy, sc.shape[-1], False
-            )
-        elif spec.family in ("logreg", "mlp", "torchmod", "pegasos",
-                             "adaline"):
+        path = self.eval_metrics_path(spec, gx.shape[0])
+        if path is None:
+            return None
+        if path == "torch":
             # large eval sets: the kernel's pairwise AUC is O(n_eval^2)
             # per block, so score with torch GEMMs and run the SYNC-FREE
             # tensor metrics (sort-based AUC) — the result rides the same
@@ -1805,7 +1835,7 @@ class HIPBackend(TorchBackend):
             # per round instead of per-op host dispatch.
             out = self._eval_metrics_torch(state, spec, local_ids, gx, gy)
         else:
-            return None
+            out = self._eval_metrics_hip(path, state, spec, local_ids, gx, gy)
         # the torch path may return POW2-PADDED rows (graph-bucketed);
         # only the first len(local_ids) are real
         valid = min(len(local_ids), out.shape[0])
@@ -1840,37 +1870,13 @@ class HIPBackend(TorchBackend):
         sigmoid is monotonic so predictions and ranks are identical.
         MLP/torchmod feed their batched forward's scores to the same
         kernel epilogue (not ``eval_mlp_wide``'s shared-set mode, see
-        :meth:`eval_metrics_launch`)."""
-        if (
-            spec.family in ("logreg", "pegasos", "adaline")
-            and gx.shape[0] <= 2048
-        ):
-            # blocks run concurrently, so the kernel's wall time tracks the
-            # PER-BLOCK pairwise-AUC work (~n_eval^2): n_eval <= 2048 keeps
-            # a block under ~100 us at any sampled-node count. Bigger eval
-            # sets (2300 samples was 58% of the 50k-node round) take the
-            # torch O(n log n) sort path
-            is_margin = spec.family in ("pegasos", "adaline")
-            out = self.ext.eval_metrics(
-                state.params,
-                local_ids.to(state.params.device, torch.int32),
-                gx,
-                gy,
-                spec.d_in,
-                1 if is_margin else spec.n_classes,
-                is_margin,
-                _EMPTY_I32,
-            )
-        elif (
-            spec.family in ("mlp", "torchmod")
-            and gx.shape[0] <= 2048
-        ):
-            sc = self.scores(state, spec, local_ids, gx)
-            out = self.ext.eval_metrics_scores(
-                sc.contiguous(), gy, sc.shape[-1], False
-            )
-        else:
+        :meth:`eval_metrics_launch`). ``None`` too where
+        :meth:`eval_metrics_path` says ``"torch"``: past 2048 rows without
+        ``GOSSIPY_EVAL_RANK=1``."""
+        path = self.eval_metrics_path(spec, gx.shape[0])
+        if path is None or path == "torch":
             return None
+        out = self._eval_metrics_hip(path, state, spec, local_ids, gx, gy)
         return metric_rows_to_dicts(out.cpu().numpy())
 
     def _part_dev(self, spec, dev):

@@ -190,6 +190,15 @@ class LogRegSpec(_PartitionMixin):
     Still bound to the LDS budget: a model row that misses it alone (4096x16),
     ``n_parts``, ``sample_size`` and the opt-in cooperative round, which
     raise a budget error past it.
+
+    A shared eval set is scored and measured in one launch
+    (``eval_metrics``, pairwise AUC) up to 2048 rows and by a torch chain
+    with an fp32 rank sum past that. ``GOSSIPY_EVAL_RANK=1`` sends every
+    size through ``eval_metrics_rank`` instead: the set in chunks of 2048
+    rows, the same scores, per chunk a sorted run of the negatives' score
+    keys, binary-search ranks of the positives and a 64-bit integer win
+    count, so the AUC is exact at any size.
+    ``HIPBackend.eval_metrics_path`` tells which route a set takes.
     """
 
     d_in: int
@@ -265,7 +274,12 @@ class MLPSpec(_PartitionMixin):
     ``GOSSIPY_MLP_WIDE=1`` / ``=0`` force / forbid the wide one. Evaluation
     follows the same split: ``eval_mlp`` while the row and 16 rows of forward
     scratch fit LDS, ``eval_mlp_wide`` past that, on per-node test shards of
-    at most 2048 rows (a shared set scores through torch). The PENS step-1
+    at most 2048 rows (a shared set scores through torch). The shared set's
+    metrics come from the pairwise kernel up to 2048 rows and from a torch
+    chain past that; ``GOSSIPY_EVAL_RANK=1`` routes them at every size
+    through ``eval_metrics_rank_scores`` (sorted chunk runs, binary-search
+    ranks, an exact integer AUC); ``HIPBackend.eval_metrics_path`` tells
+    which. The PENS step-1
     event keeps ``tick_pens_mlp_kernel`` (``w = 1``) by default and raises a
     budget error past it; ``GOSSIPY_PENS_MLP_WIDE=1`` selects the wide route
     on any shape: ``pens_mlp_score_kernel`` forwards every candidate of every

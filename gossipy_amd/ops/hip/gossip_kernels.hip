@@ -86,6 +86,12 @@
 //                           model) grid, every layer streamed through LDS in
 //                           K panels on MFMA, head logits to a workspace that
 //                           eval_metrics_kernel reads in scores mode.
+//   eval_rank_chunk_kernel, eval_rank_search_kernel,
+//   eval_rank_finalize_kernel
+//                         — K13 on a shared set of any size
+//                           (GOSSIPY_EVAL_RANK=1): per chunk of 2048 rows a
+//                           sorted run of the negatives' score keys, binary-
+//                           search ranks of the positives, an integer AUC.
 //
 // Models are tiny (57x2 logreg ... few-hundred-wide MLPs); per-launch work
 // is launch-latency bound, so kernels are built to let ONE launch cover all
@@ -2632,6 +2638,33 @@ struct EvalArgs {
 
 constexpr int EVAL_KMAX = 16;
 
+// o[0..3] = accuracy and macro precision / recall / F1 of n samples from
+// their kk x kk confusion counts (row = label, column = prediction); a
+// class without predictions or without samples contributes 0. One thread.
+DEV_INLINE void eval_macro(float* o, const int* conf, int kk, int n)
+{
+    int correct = 0;
+    float prec = 0.f, rec = 0.f, f1 = 0.f;
+    for (int c = 0; c < kk; ++c) {
+        int tp = conf[c * kk + c];
+        correct += tp;
+        int pred_tot = 0, true_tot = 0;
+        for (int t2 = 0; t2 < kk; ++t2) {
+            pred_tot += conf[t2 * kk + c];
+            true_tot += conf[c * kk + t2];
+        }
+        float p = pred_tot > 0 ? (float)tp / pred_tot : 0.f;
+        float q = true_tot > 0 ? (float)tp / true_tot : 0.f;
+        prec += p;
+        rec += q;
+        f1 += (p + q) > 0.f ? 2.f * p * q / (p + q) : 0.f;
+    }
+    o[0] = (float)correct / n;
+    o[1] = prec / kk;
+    o[2] = rec / kk;
+    o[3] = f1 / kk;
+}
+
 // Metrics epilogue shared by eval_metrics_kernel and eval_mlp_kernel: from
 // the block's staged positive-class scores s1[n_e], binarized labels
 // yb[n_e] and kk x kk confusion counts conf, write the 5-float result row
@@ -2713,27 +2746,8 @@ DEV_INLINE void eval_epilogue(float* out_row, int n_e, int kk,
 
     if (tid == 0) {
         int n = n_e;
-        int correct = 0;
-        float prec = 0.f, rec = 0.f, f1 = 0.f;
-        for (int c = 0; c < kk; ++c) {
-            int tp = conf[c * kk + c];
-            correct += tp;
-            int pred_tot = 0, true_tot = 0;
-            for (int t2 = 0; t2 < kk; ++t2) {
-                pred_tot += conf[t2 * kk + c];
-                true_tot += conf[c * kk + t2];
-            }
-            float p = pred_tot > 0 ? (float)tp / pred_tot : 0.f;
-            float q = true_tot > 0 ? (float)tp / true_tot : 0.f;
-            prec += p;
-            rec += q;
-            f1 += (p + q) > 0.f ? 2.f * p * q / (p + q) : 0.f;
-        }
         float* o = out_row;
-        o[0] = (float)correct / n;
-        o[1] = prec / kk;
-        o[2] = rec / kk;
-        o[3] = f1 / kk;
+        eval_macro(o, conf, kk, n);
         if (kk == 2) {
             int npos = npos_s, nneg = n - npos_s;
             o[4] = (npos == 0 || nneg == 0)
@@ -2923,6 +2937,278 @@ eval_mlp_kernel(EvalMlpArgs p)
     }
 
     eval_epilogue(p.out + (long)r * 5, n_e, k, s1, cs, yb, conf);
+}
+
+// ---------------------------------------------------------------------------
+// K13 at any shared-set size (GOSSIPY_EVAL_RANK=1): the eval set is cut in
+// chunks of RK_CH rows and the metrics come out of three launches, all in
+// integers until the last division.
+//   eval_rank_chunk_kernel   (chunk c, model r): scores the chunk's rows
+//       (dot_chain over the coalesced X tile, as eval_metrics_kernel, or
+//       precomputed scores), adds its confusion counts to conf[r], and for a
+//       binary problem turns the positive-class scores into ordered 32-bit
+//       keys: the NEGATIVES' keys are compacted and bitonic-sorted in LDS and
+//       written as the sorted run neg[r, c, :len], the positives' keys go
+//       unsorted to pos[r, c, :cpos[c]].
+//   eval_rank_search_kernel  (chunk c, model r): keeps the chunk's positives
+//       in registers, stages each sorted negative run of the model in LDS
+//       and finds lower and upper bound of every positive by binary search:
+//       lower + upper = 2 * (negatives below) + (negatives equal), the
+//       Mann-Whitney wins in half units, added to the 64-bit wins2[r].
+//   eval_rank_finalize_kernel (thread per model): eval_macro on the summed
+//       confusion, AUC = wins2 / 2 / (npos * nneg).
+// O(n log CH + npos * ceil(nneg / CH) * log CH) per model instead of the
+// pairwise npos * nneg, no per-row LDS beyond one chunk, and exact at any n.
+// ---------------------------------------------------------------------------
+
+constexpr int RK_CH = 2048;       // rows of a chunk = keys of a sorted run
+constexpr int RK_THREADS = 256;
+constexpr unsigned RK_PAD = 0xFFFFFFFFu;  // pads a run: no key is above it
+
+struct EvalRankArgs {
+    const float* params;  // [n_local, D]                 (scoring mode)
+    const int* nodes;     // [R] local row ids            (scoring mode)
+    const float* X;       // [n, d]                       (scoring mode)
+    const float* scores;  // [R, n, k], [R, n] margins    (scores mode)
+    const float* Y;       // [n] class index (or +-1 when is_margin)
+    int* conf;            // [R, kk, kk] summed over chunks
+    unsigned long long* wins2;  // [R] wins over (pos, neg) pairs, half units
+    int* cpos;            // [nch] positives of chunk c (the labels are shared)
+    unsigned* neg;        // [R, nch, RK_CH] sorted negative keys
+    unsigned* pos;        // [R, nch, RK_CH] positive keys
+    float* out;           // [R, 5] acc, prec, rec, f1, auc
+    int d, k, n, D, nch, R;
+    int is_margin;
+    int tile;             // X rows staged per LDS tile (scoring mode)
+};
+
+// A 32-bit key whose unsigned order is the order of the floats: -0.0 is
+// folded into +0.0 first, so scores that compare equal get equal keys. The
+// order is total: a NaN with the sign bit set lies below every number, one
+// without above +inf.
+DEV_INLINE unsigned rank_key(float s)
+{
+    unsigned u = __float_as_uint(s);
+    if ((u << 1) == 0u) u = 0u;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// One row per thread (`in` = the thread has one), whole waves: count the
+// row in the LDS confusion and, for a binary problem, append its key to the
+// chunk's positives (global) or negatives (LDS), one LDS atomic per wave
+// and label as eval_epilogue.
+DEV_INLINE void rank_emit(bool in, float sc1, int pred, float yv, int kk,
+                          bool is_margin, int* conf, unsigned* negk,
+                          unsigned* posk, int* npos_s, int* nneg_s)
+{
+    int yt = is_margin ? (yv > 0.f ? 1 : 0) : (int)yv;
+    // a label outside [0, kk) has no confusion row
+    if (in && (unsigned)yt < (unsigned)kk) atomicAdd(&conf[yt * kk + pred], 1);
+    if (kk != 2) return;
+    int lane = threadIdx.x & (WAVE - 1);
+    unsigned long long below = (1ull << lane) - 1ull;
+    bool ps = in && yt == 1;
+    bool ng = in && !ps;
+    unsigned long long mp = __ballot(ps), mn = __ballot(ng);
+    int bp = 0, bn = 0;
+    if (lane == 0) {
+        bp = atomicAdd(npos_s, __popcll(mp));
+        bn = atomicAdd(nneg_s, __popcll(mn));
+    }
+    bp = __shfl(bp, 0, WAVE);
+    bn = __shfl(bn, 0, WAVE);
+    unsigned key = rank_key(sc1);
+    if (ps) posk[bp + __popcll(mp & below)] = key;
+    if (ng) negk[bn + __popcll(mn & below)] = key;
+}
+
+template <bool SCORES>
+__global__ void __launch_bounds__(RK_THREADS)
+eval_rank_chunk_kernel(EvalRankArgs a)
+{
+    int c = blockIdx.x % a.nch, r = blockIdx.x / a.nch;
+    int tid = threadIdx.x;
+    int row0 = c * RK_CH;
+    int m_c = min(RK_CH, a.n - row0);
+    int kk = a.is_margin ? 2 : a.k;
+    __shared__ unsigned keys[RK_CH];
+    __shared__ int conf[EVAL_KMAX * EVAL_KMAX];
+    __shared__ int npos_s, nneg_s;
+    extern __shared__ float sm[];
+
+    for (int e = tid; e < kk * kk; e += RK_THREADS) conf[e] = 0;
+    if (tid == 0) { npos_s = 0; nneg_s = 0; }
+    const float* Yc = a.Y + row0;
+    size_t slab = ((size_t)r * a.nch + c) * RK_CH;
+    unsigned* posk = a.pos + slab;
+
+    if constexpr (SCORES) {
+        __syncthreads();
+        int ks = a.is_margin ? 1 : a.k;
+        const float* zs = a.scores + ((size_t)r * a.n + row0) * ks;
+        for (int base = 0; base < m_c; base += RK_THREADS) {
+            int i = base + tid;
+            bool in = i < m_c;
+            float sc1 = 0.f, yv = 0.f;
+            int pred = 0;
+            if (in) {
+                yv = Yc[i];
+                if (a.is_margin) {
+                    sc1 = zs[i];
+                    pred = sc1 >= 0.f ? 1 : 0;
+                } else {
+                    const float* z = zs + (size_t)i * a.k;
+                    float best = -1e30f;
+                    for (int j = 0; j < a.k; ++j)
+                        if (z[j] > best) { best = z[j]; pred = j; }
+                    sc1 = a.k > 1 ? z[1] : z[0];
+                }
+            }
+            rank_emit(in, sc1, pred, yv, kk, a.is_margin, conf, keys, posk,
+                      &npos_s, &nneg_s);
+        }
+    } else {
+        float* W = sm;          // D: the model row
+        float* XT = W + a.D;    // tile x d
+        copy_row(W, a.params + (long)a.nodes[r] * a.D, a.D);
+        for (int s0 = 0; s0 < m_c; s0 += a.tile) {
+            int m = min(a.tile, m_c - s0);
+            __syncthreads();  // W staged; the last tile's readers are done
+            copy_row<16>(XT, a.X + (size_t)(row0 + s0) * a.d, m * a.d);
+            __syncthreads();
+            for (int base = 0; base < m; base += RK_THREADS) {
+                int i = base + tid;
+                bool in = i < m;
+                float sc1 = 0.f, yv = 0.f;
+                int pred = 0;
+                if (in) {
+                    const float* x = XT + (long)i * a.d;
+                    yv = Yc[s0 + i];  // in flight under the scoring
+                    if (a.is_margin) {
+                        sc1 = dot_chain(0.f, W, x, a.d);
+                        pred = sc1 >= 0.f ? 1 : 0;
+                    } else {
+                        // the scores, and so argmax and key, of
+                        // eval_metrics_kernel bit for bit
+                        float best = -1e30f;
+                        for (int j = 0; j < a.k; ++j) {
+                            float acc = dot_chain(W[a.k * a.d + j],  // bias
+                                                  W + j * a.d, x, a.d);
+                            if (acc > best) { best = acc; pred = j; }
+                            if (j == 1) sc1 = acc;
+                        }
+                    }
+                }
+                rank_emit(in, sc1, pred, yv, kk, a.is_margin, conf, keys,
+                          posk, &npos_s, &nneg_s);
+            }
+        }
+    }
+    __syncthreads();
+
+    for (int e = tid; e < kk * kk; e += RK_THREADS)
+        if (conf[e]) atomicAdd(&a.conf[(size_t)r * kk * kk + e], conf[e]);
+    if (kk != 2) return;
+    int nneg = nneg_s;
+    // the counts depend on the labels alone: model 0's blocks write them
+    if (r == 0 && tid == 0) a.cpos[c] = npos_s;
+
+    // bitonic network over the next power of two of keys, padded above
+    int P = 2;
+    while (P < nneg) P <<= 1;
+    for (int i = nneg + tid; i < P; i += RK_THREADS) keys[i] = RK_PAD;
+    __syncthreads();
+    for (int k2 = 2; k2 <= P; k2 <<= 1) {
+        for (int j = k2 >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < (P >> 1); t += RK_THREADS) {
+                int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+                int p = i | j;
+                unsigned x = keys[i], y = keys[p];
+                bool up = (i & k2) == 0;
+                if ((x > y) == up) { keys[i] = y; keys[p] = x; }
+            }
+            __syncthreads();
+        }
+    }
+    unsigned* negk = a.neg + slab;
+    for (int i = tid; i < nneg; i += RK_THREADS) negk[i] = keys[i];
+}
+
+__global__ void __launch_bounds__(RK_THREADS)
+eval_rank_search_kernel(EvalRankArgs a)
+{
+    int c = blockIdx.x % a.nch, r = blockIdx.x / a.nch;
+    int tid = threadIdx.x;
+    int npos = a.cpos[c];
+    if (npos == 0) return;  // block-uniform
+    __shared__ unsigned run[RK_CH];
+    constexpr int PT = RK_CH / RK_THREADS;  // positives per thread
+    unsigned pk[PT];
+    const unsigned* posk = a.pos + ((size_t)r * a.nch + c) * RK_CH;
+#pragma unroll
+    for (int u = 0; u < PT; ++u) {
+        int i = tid + u * RK_THREADS;
+        pk[u] = i < npos ? posk[i] : 0u;
+    }
+    unsigned long long acc = 0;
+    for (int j = 0; j < a.nch; ++j) {
+        int len = min(RK_CH, a.n - j * RK_CH) - a.cpos[j];
+        if (len == 0) continue;  // block-uniform
+        const unsigned* negk = a.neg + ((size_t)r * a.nch + j) * RK_CH;
+        __syncthreads();  // the last run's searches are done
+        for (int i = tid; i < RK_CH; i += RK_THREADS)
+            run[i] = i < len ? negk[i] : RK_PAD;
+        __syncthreads();
+        unsigned w = 0;
+#pragma unroll
+        for (int u = 0; u < PT; ++u) {
+            unsigned key = pk[u];
+            // lo = keys below, hi = keys below or equal; the pad counts for
+            // neither unless the key is the pad's own value, hence the min
+            int lo = 0, hi = 0;
+            for (int s = RK_CH; s > 0; s >>= 1) {
+                if (lo + s <= RK_CH && run[lo + s - 1] < key) lo += s;
+                if (hi + s <= RK_CH && run[hi + s - 1] <= key) hi += s;
+            }
+            lo = min(lo, len);
+            hi = min(hi, len);
+            if (tid + u * RK_THREADS < npos) w += (unsigned)(lo + hi);
+        }
+        acc += w;
+    }
+    for (int off = WAVE / 2; off > 0; off >>= 1) {
+        unsigned l = (unsigned)__shfl_down((int)(unsigned)acc, off, WAVE);
+        unsigned h = (unsigned)__shfl_down((int)(acc >> 32), off, WAVE);
+        acc += ((unsigned long long)h << 32) | l;
+    }
+    if ((tid & (WAVE - 1)) == 0 && acc) atomicAdd(&a.wins2[r], acc);
+}
+
+__global__ void eval_rank_finalize_kernel(EvalRankArgs a)
+{
+    int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= a.R) return;
+    int kk = a.is_margin ? 2 : a.k;
+    float* o = a.out + (long)r * 5;
+    eval_macro(o, a.conf + (size_t)r * kk * kk, kk, a.n);
+    if (kk == 2) {
+        int npos = 0;
+        for (int c = 0; c < a.nch; ++c) npos += a.cpos[c];
+        int nneg = a.n - npos;
+        o[4] = (npos == 0 || nneg == 0)
+                   ? 0.5f
+                   : (float)(a.wins2[r] * 0.5) / ((float)npos * nneg);
+    } else {
+        o[4] = -1.f;  // AUC undefined for k > 2 (reference parity)
+    }
+}
+
+// p[0..n) = 0 on the stream (the per-call confusion and wins accumulators)
+__global__ void eval_rank_zero_kernel(int* p, long n)
+{
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n;
+         i += (long)gridDim.x * blockDim.x)
+        p[i] = 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -6126,6 +6412,138 @@ torch::Tensor eval_metrics_scores(torch::Tensor scores, torch::Tensor Y,
     return out;
 }
 
+// Device words for the chunk-sorted evaluation, one buffer per (device,
+// stream), grown when a call needs more and never shrunk or freed, as
+// mlp_wide_workspace.
+static unsigned* eval_rank_workspace(const torch::Device& dev, size_t words)
+{
+    static auto* cache =
+        new std::map<std::pair<int, hipStream_t>, torch::Tensor>();
+    torch::Tensor& t = (*cache)[{(int)dev.index(), current_stream()}];
+    if (!t.defined() || (size_t)t.numel() < words)
+        t = torch::empty({(int64_t)words},
+                         torch::dtype(torch::kInt32).device(dev));
+    return (unsigned*)t.data_ptr<int>();
+}
+
+// Most bytes of key slabs (sorted negatives + positives, 8 B per eval row
+// and model) one pass of the chunk-sorted evaluation keeps: more models than
+// fit are evaluated in several passes over the same slabs, and an eval set
+// whose single model passes it (2^27 rows) is refused.
+constexpr size_t RK_WS_LIMIT = (size_t)1 << 30;
+
+// The three launches of the chunk-sorted evaluation for R models. Of `a`
+// the operands (params/nodes/X or scores, Y), d, k, n, D, is_margin, tile
+// and out are set; dyn_smem is the chunk kernel's dynamic LDS.
+static void eval_rank_launch(EvalRankArgs a, int R, size_t dyn_smem,
+                             const torch::Device& dev)
+{
+    TORCH_CHECK(a.n > 0, "eval rank: empty eval set");
+    hipStream_t s = current_stream();
+    int kk = a.is_margin ? 2 : a.k;
+    size_t kk2 = (size_t)kk * kk;
+    bool binary = kk == 2;
+    a.nch = (a.n + RK_CH - 1) / RK_CH;
+    a.R = R;
+    size_t slab = (size_t)a.nch * RK_CH;  // keys of one model and class
+    TORCH_CHECK(!binary || 8 * slab <= RK_WS_LIMIT,
+                "eval rank workspace: the key slabs of one model on ", a.n,
+                " rows pass the ", RK_WS_LIMIT, " B limit; unset"
+                " GOSSIPY_EVAL_RANK for the torch route");
+    // models per pass: what the slab limit and a 1-D grid take
+    size_t Rs = std::min<size_t>(R, (size_t)INT_MAX / a.nch);
+    if (binary) Rs = std::min(Rs, RK_WS_LIMIT / (8 * slab));
+    // words: wins2 [R] (64-bit, first), conf [R, kk, kk], cpos [nch], slabs
+    size_t acc_words = 2 * (size_t)R + (size_t)R * kk2;
+    size_t head = (acc_words + a.nch + 1) & ~(size_t)1;
+    unsigned* ws = eval_rank_workspace(
+        dev, head + (binary ? 2 * Rs * slab : 0));
+    unsigned long long* wins2 = (unsigned long long*)ws;
+    int* conf = (int*)ws + 2 * (size_t)R;
+    a.cpos = conf + (size_t)R * kk2;
+    a.neg = ws + head;
+    a.pos = a.neg + Rs * slab;
+    int zgrid = (int)std::min<size_t>((acc_words + 255) / 256, 1024);
+    hipLaunchKernelGGL(eval_rank_zero_kernel, dim3(zgrid), dim3(256), 0, s,
+                       (int*)ws, (long)acc_words);
+    int ks = a.is_margin ? 1 : a.k;
+    for (size_t r0 = 0; r0 < (size_t)R; r0 += Rs) {
+        int rs = (int)std::min(Rs, (size_t)R - r0);
+        EvalRankArgs b = a;
+        if (b.scores) b.scores += r0 * (size_t)a.n * ks;
+        else b.nodes += r0;
+        b.conf = conf + r0 * kk2;
+        b.wins2 = wins2 + r0;
+        b.R = rs;
+        launch_kernel(b.scores ? eval_rank_chunk_kernel<true>
+                               : eval_rank_chunk_kernel<false>,
+                      rs * a.nch, RK_THREADS, dyn_smem, s, b);
+        if (binary)
+            launch_kernel(eval_rank_search_kernel, rs * a.nch, RK_THREADS, 0,
+                          s, b);
+    }
+    a.conf = conf;
+    a.wins2 = wins2;
+    launch_kernel(eval_rank_finalize_kernel, (R + 63) / 64, 64, 0, s, a);
+}
+
+torch::Tensor eval_metrics_rank(torch::Tensor params, torch::Tensor nodes,
+                                torch::Tensor X, torch::Tensor Y, int64_t d,
+                                int64_t k, bool is_margin)
+{
+    // eval_metrics on a shared eval set of any size: chunk-sorted exact AUC
+    CHECK_DEV(params); CHECK_DEV(nodes); CHECK_DEV(X); CHECK_DEV(Y);
+    TORCH_CHECK(k <= EVAL_KMAX, "n_classes > ", EVAL_KMAX, " unsupported");
+    TORCH_CHECK(X.dim() == 2 && X.size(1) == d && Y.numel() == X.size(0)
+                && X.size(0) <= INT_MAX, "eval_metrics_rank: X [n, d], Y [n]");
+    int R = nodes.size(0);
+    auto out = torch::empty({R, 5}, params.options());
+    if (R == 0) return out;
+    EvalRankArgs a{};
+    a.params = params.data_ptr<float>();
+    a.nodes = nodes.data_ptr<int>();
+    a.X = X.data_ptr<float>();
+    a.Y = Y.data_ptr<float>();
+    a.out = out.data_ptr<float>();
+    a.d = d; a.k = k; a.n = X.size(0); a.D = params.size(1);
+    a.is_margin = is_margin;
+    TORCH_CHECK((is_margin ? d : k * d + k) <= a.D,
+                "eval_metrics_rank: model row shorter than its weights");
+    // LDS: the static run, confusion and counters, then model + one X tile
+    long room = ((long)LDS_BUDGET - 10 * 1024 - (long)sizeof(float) * a.D)
+        / (long)(sizeof(float) * d);
+    TORCH_CHECK(room >= 1, "eval rank LDS budget exceeded (D=", a.D, ", d=",
+                d, ")");
+    a.tile = (int)std::min<long>({room, (long)RK_CH, 512});
+    eval_rank_launch(a, R, sizeof(float) * (a.D + (size_t)a.tile * d),
+                     params.device());
+    return out;
+}
+
+torch::Tensor eval_metrics_rank_scores(torch::Tensor scores, torch::Tensor Y,
+                                       int64_t k, bool is_margin)
+{
+    // eval_metrics_scores on [R, n, k] ([R, n] margin) scores of any n
+    CHECK_DEV(scores); CHECK_DEV(Y);
+    TORCH_CHECK(k <= EVAL_KMAX, "n_classes > ", EVAL_KMAX, " unsupported");
+    TORCH_CHECK(scores.dim() >= 2 && scores.size(1) == Y.numel()
+                && scores.numel()
+                       == scores.size(0) * Y.numel() * (is_margin ? 1 : k)
+                && Y.numel() <= INT_MAX,
+                "eval_metrics_rank_scores: scores [R, n, k], Y [n]");
+    int R = scores.size(0);
+    auto out = torch::empty({R, 5}, scores.options());
+    if (R == 0) return out;
+    EvalRankArgs a{};
+    a.scores = scores.data_ptr<float>();
+    a.Y = Y.data_ptr<float>();
+    a.out = out.data_ptr<float>();
+    a.k = k; a.n = Y.numel();
+    a.is_margin = is_margin;
+    eval_rank_launch(a, R, 0, scores.device());
+    return out;
+}
+
 // eval_mlp_kernel's LDS next to the forward scratch: model + scores + their
 // label-compacted copy + binarized labels + confusion, and the epilogue's
 // three static words (rounded up to 16 B).
@@ -7034,6 +7452,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           "fused per-node eval metrics on a shared eval set (K13)");
     m.def("eval_metrics_scores", &eval_metrics_scores,
           "K13 metrics epilogue on precomputed scores (MLP/torchmod)");
+    m.def("eval_metrics_rank", &eval_metrics_rank,
+          "eval_metrics on a shared eval set of any size: chunk-sorted runs"
+          " and binary-search ranks, exact integer AUC (params, nodes, X, Y,"
+          " d, k, is_margin)");
+    m.def("eval_metrics_rank_scores", &eval_metrics_rank_scores,
+          "eval_metrics_scores for any n_eval, same kernels (scores, Y, k,"
+          " is_margin)");
+    // rows of a chunk of the two above
+    m.attr("EVAL_RANK_CH") = RK_CH;
     // most classes the evaluation kernels take (eval_metrics*, eval_mlp)
     m.attr("EVAL_KMAX") = EVAL_KMAX;
     m.def("eval_mlp", &eval_mlp,
